@@ -2,21 +2,21 @@
 # A/B of library builds (tools/build_variant.sh) on one box: per build one short bench (serial-step
 # kernel ms per chunk) and one rocprofv3 LDS / VALU counter pass over a 4096-slot step.
 #   tools/ab_lib_pmc.sh base var1 var2 ...   (base = dect-nr-plus-sdr_amd/libdnrp.so)
-# AB_ARGS: extra bench.py arguments. Summary lines on stdout, raw data under gpurun_out/ab/.
+# AB_ARGS: extra bench.py arguments. Summary lines on stdout, raw data under bench_out/ab/.
 export TMPDIR=/tmp
-out=gpurun_out/ab
+out=bench_out/ab
 mkdir -p $out
 CNT="SQ_WAVES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES"
 for v in "$@"; do
   if [ "$v" = base ]; then lib=$PWD/dect-nr-plus-sdr_amd/libdnrp.so; else lib=$PWD/dect-nr-plus-sdr_amd/libdnrp_$v.so; fi
-  DNRP_LIB=$lib timeout -k 10 240 python bench.py --steps 2 --warmup 1 --batch 16384 --no-cpu-baseline $AB_ARGS > $out/$v.log 2>&1 || { echo "$v bench failed"; tail -5 $out/$v.log; exit 1; }
+  DNRP_LIB=$lib timeout -k 10 240 python bench.py --full --steps 2 --warmup 1 --batch 16384 --no-cpu-baseline $AB_ARGS > $out/$v.log 2>&1 || { echo "$v bench failed"; tail -5 $out/$v.log; exit 1; }
   python3 - "$v" "$out/$v.log" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 print(sys.argv[1], d['value'], {k: round(v, 3) for k, v in d['kernel_ms_per_chunk'].items()}, 'ber', round(d['check']['pdc_hard_ber'], 6), flush=True)
 PY
   if [ -z "$NO_PMC" ]; then
-    DNRP_LIB=$lib timeout -s KILL 200 rocprofv3 --pmc $CNT --output-format csv -d $out/pmc_$v -o run -- python3 bench.py --steps 1 --warmup 0 --batch 4096 --chunk 4096 --no-cpu-baseline $AB_ARGS > $out/pmc_$v.log 2>&1 || { echo "$v pmc failed"; tail -5 $out/pmc_$v.log; exit 1; }
+    DNRP_LIB=$lib timeout -s KILL 200 rocprofv3 --pmc $CNT --output-format csv -d $out/pmc_$v -o run -- python3 bench.py --full --steps 1 --warmup 0 --batch 4096 --chunk 4096 --no-cpu-baseline $AB_ARGS > $out/pmc_$v.log 2>&1 || { echo "$v pmc failed"; tail -5 $out/pmc_$v.log; exit 1; }
     python3 - "$v" "$out/pmc_$v" <<'PY'
 import csv, glob, collections, sys
 agg = collections.defaultdict(lambda: collections.defaultdict(float))

@@ -1,17 +1,17 @@
 #!/bin/bash
 # Round-3 closing measurement on the GPU box: every -m gpu test, smoke(), the default bench line
 # (with the CPU baseline), and the default bench under rocprofv3 --kernel-trace --stats with the
-# per-grid split of its closing one-stream step. Results -> gpurun_out/final/
+# per-grid split of its closing one-stream step. Results -> bench_out/final/
 set -e
-out=gpurun_out/final
+out=bench_out/final
 mkdir -p $out
 export TMPDIR=/tmp
 bash tools/gpu_tests.sh
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" > $out/smoke.log 2>&1
 tail -1 $out/smoke.log
-timeout -k 10 400 python bench.py > $out/bench_default.log 2>&1
+timeout -k 10 400 python bench.py --full > $out/bench_default.log 2>&1
 grep '^{"metric"' $out/bench_default.log | tail -1 > $out/bench_default.json
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py --no-cpu-baseline > $out/bench_rocprof.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py --full --no-cpu-baseline > $out/bench_rocprof.log 2>&1
 grep '^{"metric"' $out/bench_rocprof.log | tail -1 > $out/bench_under_rocprof.json
 stats=$(find $out/trace -name "*kernel_stats.csv" | head -1)
 trace=$(find $out/trace -name "*kernel_trace.csv" | head -1)
@@ -22,6 +22,6 @@ rm -rf $out/trace
 head -20 $out/kernel_by_grid_serial_step.txt
 python3 - <<'PY'
 import json
-d = json.loads(open('gpurun_out/final/bench_default.json').read())
+d = json.loads(open('bench_out/final/bench_default.json').read())
 print(d['value'], d['roofline'], d.get('cpu_baseline'))
 PY

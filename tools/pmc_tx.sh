@@ -1,9 +1,9 @@
 #!/bin/bash
 # SQ counter passes over the TX kernel alone (tools/tx_time.py) for the DNRP_TX_MFMA A/B:
-# gpurun_out/pmc_tx/<mode>_p<i>/  (each pass its own run, gfx950 counter-slot limits)
+# bench_out/pmc_tx/<mode>_p<i>/  (each pass its own run, gfx950 counter-slot limits)
 set -e
 export TMPDIR=/tmp
-out=gpurun_out/pmc_tx
+out=bench_out/pmc_tx
 mkdir -p $out
 for mode in 0 1; do
   i=0

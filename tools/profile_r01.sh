@@ -3,19 +3,19 @@
 # Usage: tools/profile_r01.sh <tag> [bench args...]
 set -e
 tag=$1; shift
-out=gpurun_out/prof_$tag
+out=bench_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- \
-    python3 bench.py --no-cpu-baseline "$@" > $out/trace.log 2>&1
+    python3 bench.py --full --no-cpu-baseline "$@" > $out/trace.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT \
-    --output-format csv -d $out/pmc_sq -o run -- python3 bench.py --no-cpu-baseline "$@" > $out/pmc_sq.log 2>&1
+    --output-format csv -d $out/pmc_sq -o run -- python3 bench.py --full --no-cpu-baseline "$@" > $out/pmc_sq.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVES SQ_BUSY_CYCLES SQ_INST_LEVEL_VMEM SQ_INSTS_FLAT \
-    --output-format csv -d $out/pmc_sq2 -o run -- python3 bench.py --no-cpu-baseline "$@" > $out/pmc_sq2.log 2>&1
+    --output-format csv -d $out/pmc_sq2 -o run -- python3 bench.py --full --no-cpu-baseline "$@" > $out/pmc_sq2.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -o run -- \
-    python3 bench.py --no-cpu-baseline "$@" > $out/pmc_fetch.log 2>&1
+    python3 bench.py --full --no-cpu-baseline "$@" > $out/pmc_fetch.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -o run -- \
-    python3 bench.py --no-cpu-baseline "$@" > $out/pmc_write.log 2>&1
+    python3 bench.py --full --no-cpu-baseline "$@" > $out/pmc_write.log 2>&1
 rocprofv3 -L > $out/counters.txt 2>&1 || true
 # keep the box output small: drop per-dispatch traces, keep only libdnrp rows of the PMC passes
 rm -f $out/trace/run_kernel_trace.csv

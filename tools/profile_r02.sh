@@ -1,13 +1,13 @@
 #!/bin/bash
 # Round-2 profile of one bench step (C4, one 4096-slot chunk unless args override): kernel-trace stats
 # and per-kernel PMC passes (SQ wave-cycle split + instruction mix, LDS, FETCH_SIZE, WRITE_SIZE),
-# each pass its own run (gfx950 slot limits, MI355X_MICROARCH.md). Summaries -> gpurun_out/prof_<tag>/
+# each pass its own run (gfx950 slot limits, MI355X_MICROARCH.md). Summaries -> bench_out/prof_<tag>/
 set -e
 tag=$1; shift
-out=gpurun_out/prof_$tag
+out=bench_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-args="--no-cpu-baseline --steps 1 --warmup 0 --batch 4096 $*"
+args="--full --no-cpu-baseline --steps 1 --warmup 0 --batch 4096 $*"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py $args > $out/trace.log 2>&1
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU" \

@@ -3,7 +3,7 @@
 set -e
 d=profiles/r04
 for tag in c4 c4sm fused; do
-  src=gpurun_out/prof_r04_$tag
+  src=bench_out/prof_r04_$tag
   suf=""; [ $tag != c4 ] && suf="_$tag"
   cp $src/traffic.json $d/traffic$suf.json
   cp $src/valu.json $d/valu$suf.json

@@ -3,7 +3,7 @@
 set -e
 d=profiles/r05
 for tag in c4 c4sm fused; do
-  src=gpurun_out/prof_r05_$tag
+  src=bench_out/prof_r05_$tag
   suf=""; [ $tag != c4 ] && suf="_$tag"
   cp $src/traffic.json $d/traffic$suf.json
   cp $src/valu.json $d/valu$suf.json

@@ -4,7 +4,7 @@ set -e
 d=profiles/r06
 mkdir -p $d
 for tag in c4 ypath c4sm; do
-  src=gpurun_out/prof_r06_$tag
+  src=bench_out/prof_r06_$tag
   suf=""; [ $tag != c4 ] && suf="_$tag"
   cp $src/traffic.json $d/traffic$suf.json
   cp $src/valu.json $d/valu$suf.json
