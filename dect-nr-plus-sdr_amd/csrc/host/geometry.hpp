@@ -135,4 +135,7 @@ struct rx_plan_t {
 // spatial multiplexing, whose unit is one cell carrying N_SS symbols
 rx_plan_t build_rx_plan(const maps_t& m, const std::vector<op_t>& ops, uint32_t N_eff_TX, bool pair_units = true);
 
+// dnrp_rx_sync_batch's tranche schedule (host/sync.cpp): the step frontiers of one call, the last n_steps
+std::vector<uint32_t> sync_tranches(uint32_t n_steps, uint32_t step, uint32_t stf_len, uint32_t n, uint32_t n_ant);
+
 }  // namespace dnrp::geo

@@ -215,6 +215,11 @@ int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, floa
                 v.push_back(static_cast<float>(A));
                 v.push_back(static_cast<float>(B));
             }
+        } else if (n == "sync_tranches") {  // (n_steps, step, stf_len, n, n_ant): dnrp_rx_sync_batch's step
+            // frontiers for that geometry (the last one n_steps); honours DNRP_SYNC_TRANCHE as the call does
+            if (n_arg != 5 || a(0) == 0 || a(1) == 0 || a(2) == 0 || a(3) == 0 || a(4) == 0 || a(0) > (1u << 24))
+                return DNRP_EINVAL;
+            for (const uint32_t f : geo::sync_tranches(a(0), a(1), a(2), a(3), a(4))) v.push_back(static_cast<float>(f));
         } else if (n == "stf_cover_sequence") {
             v.assign(prm::STF_COVER, prm::STF_COVER + 9);
         } else if (n == "symbol_cells") {  // (b, N_TS, N_eff_TX, N_DF): per symbol l = 0..N_DF: PCC, PDC, DRS cells

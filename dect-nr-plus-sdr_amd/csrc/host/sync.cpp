@@ -153,6 +153,44 @@ sync_tables* get_sync(dnrp_ctx* ctx, uint32_t u, uint32_t b, int* err) {
 
 }  // namespace
 
+// Tranche schedule of one call: the frontiers (exclusive step ends, ascending, the last n_steps) at
+// which the detection runs on the step sums computed so far. sync_chunk_t::search() resamples and
+// correlates only as far as its next step needs and returns at the first packet
+// (sync_chunk.cpp:159-166, 259); computing every step of every window before the first detection
+// spends most of the step-sum work behind the last requested report. A function of the sync
+// geometry and the launch geometry only, never of where a packet is expected:
+//  - first tranche 4 STFs of steps, then doubling sizes, at most 4 tranches, a remainder shorter
+//    than the first tranche joined to the one before it;
+//  - one tranche (every step, then the detection) where the search is shorter than 6 first tranches
+//    or the call's step sums are under 2^28 DECT samples (~0.6 ms of sync_steps on MI355X): there
+//    the added launches per tranche (step sums, split rounds, inline detection) are not paid back
+//    (C2: 4-sample steps, launch-latency bound).
+// DNRP_SYNC_TRANCHE (read per call: tests and A/B runs switch it): 0 = one tranche; a comma list
+// "32,64" = explicit tranche sizes in steps, the last tranche taking the rest.
+// (dnrp_query_table "sync_tranches" reports it.)
+std::vector<uint32_t> dnrp::geo::sync_tranches(uint32_t n_steps, uint32_t step, uint32_t stf_len, uint32_t n, uint32_t n_ant) {
+    std::vector<uint32_t> fr;
+    if (const char* e = std::getenv("DNRP_SYNC_TRANCHE")) {
+        uint32_t at = 0;
+        for (const char* p = e; *p;) {
+            char* q = nullptr;
+            const unsigned long v = std::strtoul(p, &q, 10);
+            if (q == p) break;
+            if (v > 0 && v < n_steps - at) fr.push_back(at += static_cast<uint32_t>(v));
+            p = *q == ',' ? q + 1 : q;
+            if (*q != ',') break;
+        }
+        fr.push_back(n_steps);
+        return fr;
+    }
+    const uint32_t t0 = std::max(1u, 4 * stf_len / step);
+    const uint64_t samples = uint64_t(n) * n_ant * n_steps * step;
+    if (n_steps >= 6 * t0 && samples >= (uint64_t(1) << 28))
+        for (uint32_t at = 0, sz = t0; fr.size() < 3 && n_steps - at >= sz + t0; sz *= 2) fr.push_back(at += sz);
+    fr.push_back(n_steps);
+    return fr;
+}
+
 extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32_t n, const float* iq,
                                   uint64_t win_stride, uint64_t ant_stride, uint32_t S_win, dnrp_sync_result* res,
                                   uint32_t* n_found, void* stream) {
@@ -234,9 +272,6 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
     a.res = ctx->sy_res.as<dev::sync_res>();
     a.n_found = ctx->sy_cnt.as<uint32_t>();
     hipStream_t st = static_cast<hipStream_t>(stream);
-    ctx->tic("sync_steps", st);
-    if (dev::launch_sync_steps(a, n, st) != hipSuccess) return DNRP_EDEVICE;
-    ctx->toc("sync_steps", st);
 #ifdef DNRP_SYNC_PROFILE
     // phase clocks of sync_detect per window (tools/sync_profile.py): averages to stderr
     static dbuf prof;
@@ -253,19 +288,35 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
     // C2 equal; same-box A/B on MI355X). Read per call (tests switch it at run time).
     const char* rd_e = std::getenv("DNRP_SYNC_ROUNDS");
     const int rounds = !dev::sync_peak_ok(a) ? 0 : rd_e ? std::max(0, std::atoi(rd_e)) : (a.n_ant > 1 ? 2 : 0);
+    // Step sums in tranches (sync_tranches above): per tranche the step-sum launch over its steps,
+    // then the detection launches up to that frontier. A window that reaches max_reports is finished
+    // (pend = 2) and the later tranches' step-sum waves of it leave at once; a window whose scan
+    // reaches the frontier saves its loop registers and goes on in the next tranche. Stream-ordered
+    // throughout; the timer names accumulate over the tranches.
+    const std::vector<uint32_t> frontier = geo::sync_tranches(a.n_steps, a.step, a.stf_len, n, a.n_ant);
     a.first = 1;
-    for (int r = 0; r < rounds; ++r) {
+    a.rounds = static_cast<uint32_t>(rounds);  // the first `rounds` detections of a window go to sync_peak, in any tranche
+    for (size_t k = 0; k < frontier.size(); ++k) {
+        a.s_lo = k ? frontier[k - 1] : 0u;
+        a.s_hi = frontier[k];
+        a.skip = k ? 1u : 0u;  // the first tranche must not read the state: not initialised yet
+        ctx->tic("sync_steps", st);
+        if (dev::launch_sync_steps(a, n, st) != hipSuccess) return DNRP_EDEVICE;
+        ctx->toc("sync_steps", st);
+        for (int r = 0; r < rounds; ++r) {
+            ctx->tic("sync_detect", st);
+            if (dev::launch_sync_detect_split(a, n, st) != hipSuccess) return DNRP_EDEVICE;
+            ctx->toc("sync_detect", st);
+            a.first = 0;
+            ctx->tic("sync_peak", st);
+            if (dev::launch_sync_peak(a, n, st) != hipSuccess) return DNRP_EDEVICE;
+            ctx->toc("sync_peak", st);
+        }
         ctx->tic("sync_detect", st);
-        if (dev::launch_sync_detect_split(a, n, st) != hipSuccess) return DNRP_EDEVICE;
+        if (dev::launch_sync_detect(a, n, st) != hipSuccess) return DNRP_EDEVICE;
         ctx->toc("sync_detect", st);
         a.first = 0;
-        ctx->tic("sync_peak", st);
-        if (dev::launch_sync_peak(a, n, st) != hipSuccess) return DNRP_EDEVICE;
-        ctx->toc("sync_peak", st);
     }
-    ctx->tic("sync_detect", st);
-    if (dev::launch_sync_detect(a, n, st) != hipSuccess) return DNRP_EDEVICE;
-    ctx->toc("sync_detect", st);
 #ifdef DNRP_SYNC_PROFILE
     if (do_prof) {
         std::vector<unsigned long long> h(size_t(n) * 32);

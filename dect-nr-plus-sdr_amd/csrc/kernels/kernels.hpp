@@ -394,11 +394,21 @@ struct sync_args {
     float2* pk;                                // [n][8]: (metric, index bits) per antenna
     uint32_t first;                            // 1: the launch starts every window from the initial state
     uint32_t ct_taps;                          // host: the sync taps equal taps_sync_9_10 (compile-time-tap kernels)
+    // tranche (host loop of dnrp_rx_sync_batch): the step-sum launch computes the steps [s_lo, s_hi),
+    // the detection launches after it scan s < s_hi only (values past the frontier are stale). One
+    // tranche: s_lo = 0, s_hi = n_steps.
+    uint32_t s_lo, s_hi;
+    uint32_t rounds;                           // split rounds per tranche = detections per window searched by sync_peak_kernel
+    uint32_t skip;                             // 1 (every tranche but a call's first): step-sum waves of finished
+                                               // windows (state[w].pend == 2) return at once
 };
 struct sync_state {  // sync_detect_kernel's loop registers (autocorrelator_detection / _peak state)
     uint32_t s_cur, ignore, nrep, pend;  // pend: 0 searching, 1 coarse peak pending, 2 finished
     uint32_t sd, s_ant;
     float s_rms, s_metric;
+    uint32_t ndet;  // detections of this call so far (false alarms included): the first sync_args::rounds
+                    // of a window go to sync_peak_kernel, the later ones to the inline search, however
+                    // the tranches cut the search
 };
 hipError_t launch_sync_steps(const sync_args& a, uint32_t n, hipStream_t st);
 hipError_t launch_sync_detect(const sync_args& a, uint32_t n, hipStream_t st);

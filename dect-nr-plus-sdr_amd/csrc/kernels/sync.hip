@@ -100,18 +100,28 @@ __host__ __device__ inline uint32_t sync_stage_cap(uint32_t L, uint32_t M, uint3
 }
 
 // ===================================================================== per-step sums
+// The step sums are computed in tranches [A.s_lo, A.s_hi) (host loop of dnrp_rx_sync_batch), the
+// detection running up to the frontier between them. From the second tranche of a call on (A.skip)
+// a window whose search has finished (max_reports reached: pend == 2) needs no further step values:
+// its waves leave at once. w is wave-uniform (w < n_win checked by the caller), so this is one scalar
+// load. The first tranche never reads the state: it is not initialised yet (A.first).
+__device__ __forceinline__ bool sync_window_done(const sync_args& A, uint32_t w) {
+    return A.skip && A.state[w].pend == 2u;
+}
+
 template <int LR, int MR, int HLR>
 __global__ void __launch_bounds__(SYNC_THREADS) sync_steps_kernel(sync_args A) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
-    const uint32_t ntile = (A.n_steps + SYNC_TILE_STEPS - 1) / SYNC_TILE_STEPS;
+    const uint32_t ntile = (A.s_hi - A.s_lo + SYNC_TILE_STEPS - 1) / SYNC_TILE_STEPS;  // tiles of the tranche
     const uint32_t tile = blockIdx.x % ntile;
     const uint32_t a = (blockIdx.x / ntile) % A.n_ant;
     const uint32_t w = blockIdx.x / (ntile * A.n_ant);
+    if (sync_window_done(A, w)) return;  // uniform over the workgroup, before any barrier
     float* taps = reinterpret_cast<float*>(smem);
     const uint32_t tap_f2 = (A.npp + 3) / 4 * 2;
     float2* lb = smem + tap_f2;
-    const uint32_t s0 = tile * SYNC_TILE_STEPS;
-    const uint32_t s1 = min(s0 + SYNC_TILE_STEPS, A.n_steps);
+    const uint32_t s0 = A.s_lo + tile * SYNC_TILE_STEPS;
+    const uint32_t s1 = min(s0 + SYNC_TILE_STEPS, A.s_hi);
     const int64_t y0 = static_cast<int64_t>(s0) * A.step - A.pattern;
     const uint32_t cnt = (s1 - s0) * A.step + A.pattern;
     float2* stage = lb + (cnt + 1) / 2 * 2;
@@ -177,22 +187,22 @@ __global__ void __launch_bounds__(64 * WPG) sync_steps_wave_kernel(sync_args A) 
     float* taps = reinterpret_cast<float*>(smem);
     const uint32_t tap_f2 = (A.npp + 3) / 4 * 2;
     const uint32_t region = sync_wave_region(LR, MR, HLR);
-    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;  // uniform
     float2* R = smem + tap_f2 + wv * region;
     const uint32_t sw = sync_wave_steps(LR, A.step, A.pattern);
-    const uint32_t parts = (A.n_steps + sw - 1) / sw;
+    const uint32_t parts = (A.s_hi - A.s_lo + sw - 1) / sw;  // parts of the tranche
     const uint32_t gw = blockIdx.x * WPG + wv;
     const uint32_t part = gw % parts;
     const uint32_t a = (gw / parts) % A.n_ant;
     const uint32_t w = gw / (parts * A.n_ant);
-    const uint32_t s0 = part * sw, s1 = min(s0 + sw, A.n_steps);
+    const uint32_t s0 = A.s_lo + part * sw, s1 = min(s0 + sw, A.s_hi);
     const int64_t y0 = static_cast<int64_t>(s0) * A.step - A.pattern;
     const uint32_t cnt = (s1 - s0) * A.step + A.pattern;
     const int64_t ms = A.m_star;
     const int64_t q0 = floordiv(y0 - ms, LR), q1 = floordiv(y0 + cnt - ms + LR - 1, LR);
     const int64_t in0 = static_cast<int64_t>(A.p_star) + MR * q0 - HLR;
     const uint32_t n_in = static_cast<uint32_t>(MR * (q1 - 1 - q0) + PB::W);
-    const bool live = w < A.n_win;
+    const bool live = w < A.n_win && !sync_window_done(A, w);  // a finished window's wave still meets the barrier
     if (live) {
         const float2* x = A.iq + w * A.win_stride + a * A.ant_stride;
         const int64_t S = A.S_win;
@@ -316,7 +326,9 @@ __global__ void __launch_bounds__(64 * SS_WPG) sync_steps_stream_kernel(sync_arg
     const uint32_t gw = blockIdx.x * WPG + wv;
     const uint32_t seg = gw % n_seg, a = (gw / n_seg) % A.n_ant, w = gw / (n_seg * A.n_ant);
     if (w >= A.n_win) return;  // no barriers below: a retired wave stalls nobody
-    const uint32_t s_a = seg * seg_steps, s_b = min(s_a + seg_steps, A.n_steps);
+    if (sync_window_done(A, w)) return;
+    // segments of the tranche [s_lo, s_hi): a segment start warms its lag history up (m_lo below)
+    const uint32_t s_a = A.s_lo + seg * seg_steps, s_b = min(s_a + seg_steps, A.s_hi);
     if (s_a >= s_b) return;
     const int64_t step = A.step, P = A.pattern;
     const int64_t m_lo = max<int64_t>(0, s_a * step - P), m_hi = s_b * step;
@@ -546,7 +558,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DNRP_SS
     const uint32_t gw = blockIdx.x;
     const uint32_t seg = gw % n_seg, a = (gw / n_seg) % A.n_ant, w = gw / (n_seg * A.n_ant);
     if (w >= A.n_win) return;
-    const uint32_t s_a = seg * seg_steps, s_b = min(s_a + seg_steps, A.n_steps);
+    if (sync_window_done(A, w)) return;
+    const uint32_t s_a = A.s_lo + seg * seg_steps, s_b = min(s_a + seg_steps, A.s_hi);  // segments of the tranche
     if (s_a >= s_b) return;
     const int64_t step = A.step, P = A.pattern;
     const int64_t m_lo = max<int64_t>(0, s_a * step - P), m_hi = s_b * step;
@@ -885,7 +898,7 @@ __global__ void __launch_bounds__(SYNC_THREADS) SYNC_DETECT_ATTR sync_detect_ker
     pl.ckp = reinterpret_cast<double*>(pl.ckc + (region + 15) / 16 + 2);
     pl.met = reinterpret_cast<float*>(pl.ckp + (region + 15) / 16 + 2);
     // loop registers: the initial state, or the state a split launch saved
-    sync_state S0{4u, A.stf_len + A.pattern, 0u, 0u, 0u, 0u, 0.f, 0.f};
+    sync_state S0{4u, A.stf_len + A.pattern, 0u, 0u, 0u, 0u, 0.f, 0.f, 0u};
     if (!A.first) S0 = A.state[w];
     if (S0.pend == 2) return;  // uniform: finished in an earlier launch
     if (!SPLIT && LR > 1) stage_copy<4>(taps, A.taps_pp, A.npp, threadIdx.x, blockDim.x);
@@ -899,7 +912,7 @@ __global__ void __launch_bounds__(SYNC_THREADS) SYNC_DETECT_ATTR sync_detect_ker
     const uint32_t det_p = (SYNC_THREADS + np + 3) / 4 * 4, det_c = SYNC_THREADS + nc;
     float2* dc = stage;
     float* dp = reinterpret_cast<float*>(dc + A.n_ant * det_c);
-    uint32_t nrep = S0.nrep, s_cur = S0.s_cur, ignore = S0.ignore;
+    uint32_t nrep = S0.nrep, s_cur = S0.s_cur, ignore = S0.ignore, ndet = S0.ndet;
     bool resume = S0.pend == 1;  // a saved detection whose coarse peaks sync_peak_kernel has searched
     SYNC_STAMP(0);
     while (nrep < A.max_reports) {
@@ -921,10 +934,13 @@ __global__ void __launch_bounds__(SYNC_THREADS) SYNC_DETECT_ATTR sync_detect_ker
             // ---------------- detection: first step at or after s_cur meeting the conditions
             if (threadIdx.x == 0) s_min = 0x7FFFFFFF;
             __syncthreads();
-            for (uint32_t base = s_cur; base < A.n_steps; base += blockDim.x) {
+            // only steps below the frontier s_lim = A.s_hi exist (the step sums computed so far in this
+            // call); the staging below never reads past it: what lies there is stale from earlier calls
+            const uint32_t s_lim = A.s_hi;
+            for (uint32_t base = s_cur; base < s_lim; base += blockDim.x) {
                 // the batch's step values of every antenna in LDS (one coalesced round trip); steps a
                 // detection can evaluate have s - (np - 1) >= 0 (ignore >= stf_len + pattern)
-                const uint32_t nb = min(blockDim.x, A.n_steps - base);
+                const uint32_t nb = min(blockDim.x, s_lim - base);
                 const uint32_t lo_p = base >= np - 1 ? base - (np - 1) : 0u, lo_c = base >= nc - 1 ? base - (nc - 1) : 0u;
                 const uint32_t len_p = base + nb - lo_p, len_c = base + nb - lo_c;
                 for (uint32_t a = 0; a < A.n_ant; ++a) {
@@ -933,7 +949,7 @@ __global__ void __launch_bounds__(SYNC_THREADS) SYNC_DETECT_ATTR sync_detect_ker
                 }
                 __syncthreads();
                 const uint32_t s = base + threadIdx.x;
-                if (s < A.n_steps && (s + 1) * A.step >= ignore) {
+                if (s < s_lim && (s + 1) * A.step >= ignore) {
                     for (uint32_t a = 0; a < A.n_ant; ++a) {
                         det_eval e;
                         if (detect_eval(A, dp + a * det_p - lo_p, dc + a * det_c - lo_c, s, e)) {
@@ -949,7 +965,16 @@ __global__ void __launch_bounds__(SYNC_THREADS) SYNC_DETECT_ATTR sync_detect_ker
             }
             sd = s_min;
             __syncthreads();
-            if (sd == 0x7FFFFFFF) break;
+            if (sd == 0x7FFFFFFF) {
+                if (s_lim < A.n_steps) {
+                    // the scan reached the frontier with reports still to find: the window is not
+                    // finished. The loop registers wait for the next tranche (every step below s_lim
+                    // is evaluated or ignored; the reports found so far stay in res)
+                    if (threadIdx.x == 0) A.state[w] = sync_state{max(s_cur, s_lim), ignore, nrep, 0u, 0u, 0u, 0.f, 0.f, ndet};
+                    return;
+                }
+                break;
+            }
             if (threadIdx.x == 0) {
                 for (uint32_t a = 0; a < A.n_ant; ++a) {
                     det_eval e;
@@ -963,10 +988,14 @@ __global__ void __launch_bounds__(SYNC_THREADS) SYNC_DETECT_ATTR sync_detect_ker
             }
             __syncthreads();
             if constexpr (SPLIT) {  // leave with the detection pending: sync_peak_kernel searches its peaks
+                // a window's first A.rounds detections only, as with one tranche (one per split round):
+                // a later one is left where it is for the inline form, which finds it again from s_cur
                 if (threadIdx.x == 0)
-                    A.state[w] = sync_state{s_cur, ignore, nrep, 1u, static_cast<uint32_t>(sd), s_ant, s_rms, s_metric};
+                    A.state[w] = ndet < A.rounds ? sync_state{s_cur, ignore, nrep, 1u, static_cast<uint32_t>(sd), s_ant, s_rms, s_metric, ndet + 1}
+                                                 : sync_state{s_cur, ignore, nrep, 0u, 0u, 0u, 0.f, 0.f, ndet};
                 return;
             }
+            ++ndet;
         }
         SYNC_STAMP(1);
         s_cur = static_cast<uint32_t>(sd) + 1;
@@ -1677,15 +1706,19 @@ hipError_t launch_sync_steps(const sync_args& a, uint32_t n, hipStream_t st) {
     // DNRP_SYNC_STREAM=0 selects the wave kernel below (read per call: tests switch it at run time)
     const char* ss_e = std::getenv("DNRP_SYNC_STREAM");
     const int ss_env = ss_e ? std::atoi(ss_e) : 1;
+    // the tranche [s_lo, s_hi) of the window's steps: only the segments / parts / tiles that cover it
+    // are launched (one tranche over all steps: the grids below are the whole-window ones)
+    if (a.s_lo >= a.s_hi || a.s_hi > a.n_steps) return hipErrorInvalidValue;
+    const uint32_t n_rng = a.s_hi - a.s_lo;
     if (ss_env && a.L == 9 && a.M == 10 && a.hl == 24 && a.step % 4 == 0 && a.step >= 4 &&
         64u * 9u + a.step + a.pattern + 9u <= SS_RING) {
         // segments of ~32 chunks per (window, antenna): enough waves to fill the chip, little warm-up
         // segments of at most DNRP_SS_SEG_CHUNKS chunks, balanced: ceil(n_steps / max) segments of
         // equal length (a short last segment leaves its waves idle at the tail)
         const uint32_t seg_max = std::max(1u, (DNRP_SS_SEG_CHUNKS * 64u * 9u) / a.step);
-        const uint32_t n_seg0 = (a.n_steps + seg_max - 1) / seg_max;
-        const uint32_t seg_steps = std::max(1u, (a.n_steps + n_seg0 - 1) / n_seg0);
-        const uint32_t n_seg = (a.n_steps + seg_steps - 1) / seg_steps;
+        const uint32_t n_seg0 = (n_rng + seg_max - 1) / seg_max;
+        const uint32_t seg_steps = std::max(1u, (n_rng + n_seg0 - 1) / n_seg0);
+        const uint32_t n_seg = (n_rng + seg_steps - 1) / seg_steps;
         const uint64_t waves = uint64_t(n) * a.n_ant * n_seg;
         const size_t lds = SS_WPG * size_t(ss_inbuf<9, 10, 24>() + SS_RING) * sizeof(float2);
         const dim3 g(static_cast<uint32_t>((waves + SS_WPG - 1) / SS_WPG)), b(64 * SS_WPG);
@@ -1712,13 +1745,13 @@ hipError_t launch_sync_steps(const sync_args& a, uint32_t n, hipStream_t st) {
     }
     if (a.L == 9 && a.M == 10 && a.hl == 24) {
         const uint32_t sw = sync_wave_steps(9, a.step, a.pattern);
-        const uint32_t waves = n * a.n_ant * ((a.n_steps + sw - 1) / sw);
+        const uint32_t waves = n * a.n_ant * ((n_rng + sw - 1) / sw);
         const size_t lds = (a.npp + 3) / 4 * 2 * sizeof(float2) + SYNC_WPG * size_t(sync_wave_region(9, 10, 24)) * sizeof(float2);
         hipLaunchKernelGGL((sync_steps_wave_kernel<9, 10, 24, SYNC_WPG>), dim3((waves + SYNC_WPG - 1) / SYNC_WPG),
                            dim3(64 * SYNC_WPG), lds, st, a);
         return hipGetLastError();
     }
-    const uint32_t ntile = (a.n_steps + SYNC_TILE_STEPS - 1) / SYNC_TILE_STEPS;
+    const uint32_t ntile = (n_rng + SYNC_TILE_STEPS - 1) / SYNC_TILE_STEPS;
     const uint32_t cnt = SYNC_TILE_STEPS * a.step + a.pattern;
     const size_t lds = (a.npp + 3) / 4 * 2 * sizeof(float2) + (cnt + 1) / 2 * 2 * sizeof(float2) +
                        sync_stage_cap(a.L, a.M, a.hl, cnt) * sizeof(float2);
