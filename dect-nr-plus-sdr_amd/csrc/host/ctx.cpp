@@ -1293,10 +1293,12 @@ int dnrp_rx_pdc_batch(dnrp_ctx* ctx, uint32_t m, const dnrp_pdc_req* req, const 
                 ctx->tic("rx_epoch", st);
                 if (dev::launch_rx_epoch(x, ng, st) != hipSuccess) return DNRP_EDEVICE;
                 ctx->toc("rx_epoch", st);
-            } else if (G && ng > G && t2->q.N_DF_symb > t->pcc_max && fa.stream && dev::rx_fft_wave_path(fa)) {
+            } else if (G && ng > G && t2->q.N_DF_symb > t->pcc_max) {
                 // packet groups: front end of group g on st, back end of group g on rx_aux once that
                 // front end is done, so group g+1's front end runs beside group g's back end and the
-                // back end reads Y (plain stores) while it is still in the L2 / Infinity Cache
+                // back end reads Y (plain stores) while it is still in the L2 / Infinity Cache.
+                // Every front end takes it (each launch selects its packets through sel); y_plain is
+                // read by the streaming wave kernel only (N_b_DFT_os = 1024), the others store as ever
                 if (!ctx->rx_aux) {
                     HIPCHK(hipStreamCreateWithFlags(&ctx->rx_aux, hipStreamNonBlocking));
                     HIPCHK(hipEventCreateWithFlags(&ctx->rx_fork, hipEventDisableTiming));

@@ -323,14 +323,24 @@ int oracle_tx(const uint32_t* cfg, const uint32_t* psdef, const uint32_t* desc_u
 
 // meta out: [0..7] rms, 8 cfo_fine_rad, 9 sto_fractional, 10 snr_pcc_db, 11 snr_pdc_db,
 //           12 mimo N_TS_other, 13 tm_3_7_beamforming_idx, 14 tm_3_7_beamforming_reciprocal_idx
-int oracle_rx(const uint32_t* cfg, const uint32_t* psdef, uint32_t N_RX, const float* iq, uint32_t S_in,
-              int64_t fine_peak, double cfo_rad, uint32_t network_id, uint32_t plcf_type, int16_t* pcc_llr,
-              int16_t* pdc_llr, float* pcc_llr_f, float* pdc_llr_f, float* meta, int use_float, const float* sync_rms,
-              int sm_mmse) {
+//
+// oracle_rx_picks: the same, plus the Wiener-LUT pick trace and the test-only pick overrides.
+// pick_force >= 0 uses that profile at every DRS operation, pick_stale != 0 the previous DRS operation's
+// pick (rx_in_t). picks (nullable): up to picks_cap pairs (profile, SNR estimate in dB at the pick), one
+// per DRS operation in order, the profile being the one the estimate selects whatever the override;
+// *n_picks the number of DRS operations.
+int oracle_rx_picks(const uint32_t* cfg, const uint32_t* psdef, uint32_t N_RX, const float* iq, uint32_t S_in,
+                    int64_t fine_peak, double cfo_rad, uint32_t network_id, uint32_t plcf_type, int16_t* pcc_llr,
+                    int16_t* pdc_llr, float* pcc_llr_f, float* pdc_llr_f, float* meta, int use_float,
+                    const float* sync_rms, int sm_mmse, int pick_force, int pick_stale, float* picks,
+                    uint32_t picks_cap, uint32_t* n_picks) {
     try {
         packet_sizes_t q;
         if (!get_packet_sizes(to_psdef(psdef), q)) return -1;
+        if (pick_force > 2) return -1;
         rx_in_t in{iq, N_RX, S_in, fine_peak, cfo_rad, network_id, plcf_type, sync_rms, sm_mmse != 0};
+        in.pick_force = pick_force;
+        in.pick_stale = pick_stale != 0;
         rx_out_t o;
         if (use_float)
             rx_packet<float>(to_cfg(cfg), q, in, o);
@@ -350,11 +360,24 @@ int oracle_rx(const uint32_t* cfg, const uint32_t* psdef, uint32_t N_RX, const f
         // MIMO_REF_UNDEFINED (the reference asserts / throws) -> -2
         meta[13] = o.mimo_idx == MIMO_REF_UNDEFINED ? -2.f : static_cast<float>(o.mimo_idx);
         meta[14] = o.mimo_idx_reciprocal == MIMO_REF_UNDEFINED ? -2.f : static_cast<float>(o.mimo_idx_reciprocal);
+        if (n_picks) *n_picks = static_cast<uint32_t>(o.lut_picks.size());
+        for (uint32_t i = 0; picks && i < picks_cap && i < o.lut_picks.size(); ++i) {
+            picks[2 * i] = static_cast<float>(o.lut_picks[i].first);
+            picks[2 * i + 1] = o.lut_picks[i].second;
+        }
         return 0;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "oracle_rx: %s\n", e.what());
         return -2;
     }
+}
+
+int oracle_rx(const uint32_t* cfg, const uint32_t* psdef, uint32_t N_RX, const float* iq, uint32_t S_in,
+              int64_t fine_peak, double cfo_rad, uint32_t network_id, uint32_t plcf_type, int16_t* pcc_llr,
+              int16_t* pdc_llr, float* pcc_llr_f, float* pdc_llr_f, float* meta, int use_float, const float* sync_rms,
+              int sm_mmse) {
+    return oracle_rx_picks(cfg, psdef, N_RX, iq, S_in, fine_peak, cfo_rad, network_id, plcf_type, pcc_llr, pdc_llr,
+                           pcc_llr_f, pdc_llr_f, meta, use_float, sync_rms, sm_mmse, -1, 0, nullptr, 0, nullptr);
 }
 
 // CPU baseline: n_packets TX+RX loopback slot-pairs (float path), one packet per thread at a time

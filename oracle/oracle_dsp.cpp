@@ -351,6 +351,10 @@ int16_t llr_to_i16(double v) {
     return static_cast<int16_t>(std::max(-32768.0, std::min(32767.0, r)));
 }
 
+// descrambling negation of a quantised LLR, saturating: -(-32768) = +32767, never a full-scale LLR
+// of the wrong sign (a plain int16 negation wraps back to -32768). DESIGN.md section 7.
+int16_t neg_sat_i16(int16_t v) { return v == INT16_MIN ? INT16_MAX : static_cast<int16_t>(-v); }
+
 namespace {
 // channel LUTs are init-time objects in the reference (rx_synced.cpp:147-157): build once
 const chest_lut_t& cached_lut(uint32_t Nsv, uint32_t b, uint32_t b_max, uint32_t u_max, int p, const chest_stats_t& st) {
@@ -385,6 +389,7 @@ struct rx_state_t {
     std::vector<chest_stats_t> prof;
     std::vector<chest_lut_t> lut0, lut_lr;
     int lut_eff = -1;
+    int lut_true = -1;  // the SNR estimate's own pick at the latest DRS operation (rx_in_t::pick_stale)
     double nv_eff = 0.0;  // noise variance per RX cell at the latest LUT pick (MMSE regularisation)
     uint32_t ps_idx = 0, rel = 0, l_abs = 1, ts_first = 0, ts_last = 0;
     bool mode_lr = false;
@@ -593,6 +598,13 @@ struct rx_state_t {
                 idx = i;
             }
         }
+        out.lut_picks.emplace_back(idx, snr);
+        const int prev = lut_true;
+        lut_true = idx;
+        if (in.pick_force >= 0)
+            idx = in.pick_force;
+        else if (in.pick_stale && prev >= 0)
+            idx = prev;
         lut_eff = idx;
         nv_eff = snr_N > 0 ? snr_N / static_cast<double>(snr_N_cnt) : 0.0;
     }
@@ -888,13 +900,13 @@ struct rx_state_t {
         const auto cp = gold_sequence(0x44454354u, 196);
         for (uint32_t i = 0; i < 196; ++i)
             if (cp[i]) {
-                out.pcc_llr[i] = static_cast<int16_t>(-out.pcc_llr[i]);
+                out.pcc_llr[i] = neg_sat_i16(out.pcc_llr[i]);
                 out.pcc_llr_f[i] = -out.pcc_llr_f[i];
             }
         const auto cs = gold_sequence(pdc_c_init(in.network_id, in.plcf_type), ps.G);
         for (uint32_t i = 0; i < ps.G; ++i)
             if (cs[i]) {
-                out.pdc_llr[i] = static_cast<int16_t>(-out.pdc_llr[i]);
+                out.pdc_llr[i] = neg_sat_i16(out.pdc_llr[i]);
                 out.pdc_llr_f[i] = -out.pdc_llr_f[i];
             }
     }

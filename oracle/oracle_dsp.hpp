@@ -3,6 +3,7 @@
 
 #include <complex>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "oracle.hpp"
@@ -33,6 +34,11 @@ struct rx_in_t {  // sync_report_t subset + HARQ scrambling parameters
     uint32_t network_id, plcf_type;
     const float* sync_rms = nullptr;  // sync_report_t::rms_array[8] (nullable)
     bool sm_mmse = false;             // demodulate N_SS > 1 by MMSE (not in the reference, rx_synced.cpp:1331)
+    // test-only mutations of the Wiener-LUT pick (tests/test_rx_lut_inputs.py: the parity gate must see
+    // them): pick_force >= 0 uses that profile at every DRS operation, pick_stale uses the previous DRS
+    // operation's pick (the first operation keeps its own)
+    int pick_force = -1;
+    bool pick_stale = false;
 };
 
 struct rx_out_t {
@@ -41,6 +47,9 @@ struct rx_out_t {
     std::vector<float> rms;
     float cfo_fine_rad = 0, sto_fractional = 0, snr_pcc_db = 0, snr_pdc_db = 0;
     uint32_t mimo_N_TS_other = 0, mimo_idx = 0, mimo_idx_reciprocal = 0;  // mimo_report_t (MIMO_REF_UNDEFINED: none)
+    // every DRS operation in order (PCC phase first): the profile the SNR estimate selects (before any
+    // test-only override) and that estimate in dB
+    std::vector<std::pair<int, float>> lut_picks;
 };
 
 struct dims_t {
@@ -53,6 +62,7 @@ struct dims_t {
 uint32_t pdc_c_init(uint32_t network_id, uint32_t plcf_type);
 void demap_float(const cd& y, uint32_t N_bps, double* L);
 int16_t llr_to_i16(double v);
+int16_t neg_sat_i16(int16_t v);
 
 template <typename R>
 void tx_packet(const cfg_t& cfg, const packet_sizes_t& ps, const tx_desc_t& d, const uint8_t* pcc_d,

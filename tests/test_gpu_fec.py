@@ -225,12 +225,15 @@ def test_gpu_decoders_match_numpy_oracle():
             assert np.array_equal(np.unpackbits(got[i, : 5 * types[i]]), bits_o)
 
 
-def test_gpu_encoder_matches_host():
+def test_gpu_encoder_matches_host(monkeypatch):
     """dnrp_pdc_encode_batch against dnrp_pdc_encode (itself bit-exact against the numpy oracle):
-    mixed sizes, Z, modulation orders and redundancy versions in one call."""
+    mixed sizes, Z, modulation orders and redundancy versions in one call. The G = 7001, Qm = 1 packet
+    has code blocks that are no whole bytes, so the batch goes through the packed scratch and
+    fec_pack_kernel (the launch count says so); test_gpu_encoder_direct_mode covers the other mode."""
     import dnrp
     import dnrp.fec as FE
     import fec_np as ON  # noqa: F401
+    monkeypatch.setenv("DNRP_TIMING", "1")
     phy = dnrp.Phy(1, 1, 1, max_batch=1)
     rng = np.random.default_rng(4)
     cfgs, tbs = [], []
@@ -252,6 +255,73 @@ def test_gpu_encoder_matches_host():
     for i in range(m):
         ref = FE.pdc_encode(cfgs[i], tbs[i])
         assert (g[i, : len(ref)] == ref).all(), (i, cfgs[i].N_TB_bits, cfgs[i].G)
+        assert len(ref) == (cfgs[i].G + 7) // 8 and (g[i, len(ref):] == 0xAB).all(), (i, "bytes past the row's end")
+    assert phy.kernel_time_total("fec_pack")[1] > 0 and phy.kernel_time_total("fec_encode")[1] > 0
+
+
+# direct mode: (N_TB_bits, Qm, G, Z, rv) -- every code block starts on a byte of its d row and has whole
+# bytes (fec.cpp enc_plan::bytes), so fec_encode_kernel stores 512-byte chunks of each block straight
+# into d through its LDS stage and no pack kernel runs. The default for every 256-QAM batch.
+DIRECT_CASES = [
+    (363464, 8, 486640, 6144, 0),   # the C4 transport block: 60 blocks of 2 sizes and 2 lengths E
+    (136, 8, 320, 6144, 0),         # one block of 40 bytes: less than one 64-byte store row
+    (1000, 8, 4096, 6144, 0),       # E / 8 = 512: the last word of a full chunk is the block's last word
+    (1000, 8, 4104, 6144, 0),       # E / 8 = 513: a second chunk of one byte, from a partial last word
+    (136, 8, 600, 6144, 0),         # E % 64 = 24: a partial last word in the first chunk
+    (40008, 8, 60008, 2048, 1),     # C > 1 with Z = 2048, two lengths E, rv 1
+    (40008, 8, 60000, 2048, 2),     # ... rv 2
+    (18456, 8, 36000, 2048, 3),     # ... rv 3
+    (2984, 4, 7000, 6144, 0),       # 16-QAM, one block, G a whole number of bytes
+    (296, 2, 648, 6144, 0),         # QPSK, one block, G a whole number of bytes
+]
+
+
+def test_gpu_encoder_direct_mode(monkeypatch):
+    """dnrp_pdc_encode_batch in direct mode against dnrp_pdc_encode byte for byte, over the edges of the
+    chunked store (fec.hip fec_encode_kernel: chunks of 64 words = 512 bytes, the tail chunk's byte count,
+    a partial last word), with d rows poisoned and wider than the longest row: nothing past a row's
+    (G + 7) // 8 bytes is written. The launch counts prove the mode: no fec_pack launch."""
+    import dnrp
+    import dnrp.fec as FE
+    import fec_np as ON
+    monkeypatch.setenv("DNRP_TIMING", "1")
+    phy = dnrp.Phy(1, 1, 1, max_batch=1)
+    rng = np.random.default_rng(6)
+    cfgs, tbs, e_bytes, multi = [], [], set(), []
+    for tbs_bits, Qm, G, Z, rv in DIRECT_CASES:
+        C, Ks, F = ON.cbsegm(tbs_bits, Z)
+        assert F == 0 and G % Qm == 0, (tbs_bits, Z, F)
+        # the direct-mode condition, restated (TS 36.212 5.1.4.1.2 E_r; blocks back to back in the row)
+        Gp, start = G // Qm, 0
+        for r in range(C):
+            E = Qm * (Gp // C) if r <= C - Gp % C - 1 else Qm * -(-Gp // C)
+            assert start % 8 == 0 and E % 8 == 0, (tbs_bits, Qm, G, r, start, E)
+            start += E
+            e_bytes.add(E // 8)
+        assert start == G
+        if C > 1:
+            multi.append((Z, rv, len({Ks[0], Ks[-1]})))
+        cfgs.append(FE.fec_cfg(tbs_bits, Qm, G, Z=Z, rv=rv))
+        tbs.append(rng.integers(0, 256, tbs_bits // 8, dtype=np.uint8))
+    # the edges the cases are there for
+    assert min(e_bytes) < 64 and 512 in e_bytes and 513 in e_bytes and any(8 * e % 64 for e in e_bytes)
+    assert {rv for Z, rv, _ in multi if Z == 2048} >= {1, 2, 3} and any(k == 2 for _, _, k in multi)
+    assert {c.N_bps for c in cfgs} == {2, 4, 8}
+    m = len(cfgs)
+    dev = torch.device("cuda:0")
+    tb = np.zeros((m, max(c.N_TB_bits for c in cfgs) // 8 + 1), np.uint8)
+    for i in range(m):
+        tb[i, : len(tbs[i])] = tbs[i]
+    d = torch.full((m, max((c.G + 7) // 8 for c in cfgs) + 5), 0xAB, dtype=torch.uint8, device=dev)
+    FE.pdc_encode_batch(phy, cfgs, torch.from_numpy(tb).to(dev), d)
+    g = d.cpu().numpy()
+    for i in range(m):
+        ref = FE.pdc_encode(cfgs[i], tbs[i])
+        assert len(ref) == cfgs[i].G // 8
+        assert (g[i, : len(ref)] == ref).all(), (i, DIRECT_CASES[i], int(np.flatnonzero(g[i, : len(ref)] != ref)[0]))
+        assert (g[i, len(ref):] == 0xAB).all(), (i, DIRECT_CASES[i], "bytes past the row's end")
+    assert phy.kernel_time_total("fec_pack")[1] == 0
+    assert phy.kernel_time_total("fec_encode")[1] > 0
 
 
 def test_gpu_plcf_decoder_matches_host():

@@ -194,20 +194,47 @@ def test_rx_parity(name, stride=2):
     _rx_parity(name, stride)
 
 
-def _rx_parity(name, stride=2):
-    """Runs one RX parity case; returns the context (its kernel timers, with DNRP_TIMING=1)."""
+def _rx_parity(name, stride=2, prepared=None):
+    """Runs one RX parity case; returns the context (its kernel timers, with DNRP_TIMING=1).
+    prepared: windows built elsewhere instead of the case's own (_lut_prepared), as the tuple (phy, ps,
+    ops, windows, reports, nids, types, pdc, hard, oracle) -- hard[i]: packet i's uncoded hard decisions
+    are checked, oracle(i): the oracle's RX of packet i."""
     import dnrp
-    rng = np.random.default_rng(11)
-    phy, ps, ops, ocf = _ctx(name, stride=stride)
-    snrs, cb = CASES[name][3], CASES[name][4]
+    if prepared is None:
+        rng = np.random.default_rng(11)
+        phy, ps, ops, ocf = _ctx(name, stride=stride)
+        snrs, cb = CASES[name][3], CASES[name][4]
+        windows, reports, nids, types, _, pdc = _rx_windows(rng, name, phy, ps, ops, ocf, snrs, cb)
+        # packet 0's sync report carries an RMS for antenna 0 only: kept, the others estimated
+        # (RX_SYNCED_PARAM_RMS_KEEP_VALUES_PROVIDED_BY_SYNC, rx_synced.cpp:620-655)
+        reports[0].rms[0] = 0.123
+        sync_rms = [[0.123] + [0.0] * 7] + [None] * (len(windows) - 1)
+        hard = [s >= 20.0 for s in snrs]  # uncoded hard decisions well above the demapping noise floor
+
+        def oracle(i):
+            return O.rx(ocf, ops, windows[i], reports[i].fine_peak_time,
+                        float(np.float32(reports[i].cfo_fractional_rad)), nids[i], types[i], sync_rms=sync_rms[i])
+    else:
+        phy, ps, ops, windows, reports, nids, types, pdc, hard, oracle = prepared
     sz = phy.packet_sizes(ps)
+    g_pcc, g_pdc, rep1, rep2 = _gpu_rx(phy, ps, sz, windows, reports, nids, types)
+    for i in range(len(windows)):
+        r = oracle(i)
+        _check_rx((name, i), g_pcc[i], g_pdc[i], rep1[i], rep2[i], r)
+        if i == 0:
+            assert rep1[0].rms[0] == np.float32(0.123) and r["rms"][0] == np.float32(0.123)
+        if hard[i]:
+            bits = np.unpackbits(pdc[i])[: sz["G"]]
+            assert np.mean(bits != (g_pdc[i] > 0)) < 2e-2, (name, i)
+    return phy
+
+
+def _gpu_rx(phy, ps, sz, windows, reports, nids, types):
+    """One PCC batch and one PDC batch of all windows, with reports: (PCC LLRs, PDC LLRs, PCC reports,
+    PDC reports)."""
+    import dnrp
     S = sz["N_samples_packet_os_rs"]
-    windows, reports, nids, types, _, pdc = _rx_windows(rng, name, phy, ps, ops, ocf, snrs, cb)
     n, n_rx = len(windows), phy.cfg.N_TX_max
-    # packet 0's sync report carries an RMS for antenna 0 only: kept, the others estimated
-    # (RX_SYNCED_PARAM_RMS_KEEP_VALUES_PROVIDED_BY_SYNC, rx_synced.cpp:620-655)
-    reports[0].rms[0] = 0.123
-    sync_rms = [[0.123] + [0.0] * 7] + [None] * (n - 1)
     dev = torch.device("cuda:0")
     iq = torch.from_numpy(np.stack(windows).view(np.float32).reshape(n, n_rx, S, 2)).to(dev)
     pcc_llr = torch.zeros((n, 196), dtype=torch.int16, device=dev)
@@ -216,17 +243,7 @@ def _rx_parity(name, stride=2):
     rep2 = phy.rx_pdc_batch([dnrp.PdcReq(ps, i, nids[i], types[i]) for i in range(n)], iq, pdc_llr,
                             want_report=True)
     phy.sync()
-    g_pcc, g_pdc = pcc_llr.cpu().numpy(), pdc_llr.cpu().numpy()
-    for i in range(n):
-        r = O.rx(ocf, ops, windows[i], reports[i].fine_peak_time, float(np.float32(reports[i].cfo_fractional_rad)),
-                 nids[i], types[i], sync_rms=sync_rms[i])
-        _check_rx((name, i), g_pcc[i], g_pdc[i], rep1[i], rep2[i], r)
-        if i == 0:
-            assert rep1[0].rms[0] == np.float32(0.123) and r["rms"][0] == np.float32(0.123)
-        if snrs[i] >= 20.0:  # uncoded hard decisions well above the demapping noise floor
-            bits = np.unpackbits(pdc[i])[: sz["G"]]
-            assert np.mean(bits != (g_pdc[i] > 0)) < 2e-2, (name, i)
-    return phy
+    return pcc_llr.cpu().numpy(), pdc_llr.cpu().numpy(), rep1, rep2
 
 
 @pytest.mark.parametrize("name,stride", [("tm5_u2b4", 1), ("tm5_u2b4", 3), ("C4", 1), ("C4", 3), ("mrc2_64qam", 3),
@@ -663,3 +680,142 @@ def _full_chunk_edges(name, n):
         win = rx[i].cpu().numpy().view(np.complex64)[..., 0]
         r = O.rx(ocf, ops, win, 0, float(np.float32(-cfo_dect[i])), 100 + i % 6, 1 + i % 2)
         _check_rx((name, i), pcc_llr[i].cpu().numpy(), pdc_llr[i].cpu().numpy(), None, None, r)
+
+
+# ---- the other Wiener-LUT profiles, and a pick that changes inside a packet (tests/lut_cases.py; the CPU
+# file tests/test_rx_lut_inputs.py shows from the oracle alone that these windows pick profiles 0, 1, 2
+# and 2 -> 1 / 1 -> 0 clear of the boundaries, and that the gate sees a wrong pick on them)
+def _lut_prepared(table, lr=1, stride=2, max_batch=8):
+    """All packets of a lut_cases table as one batch, in the form _rx_parity takes."""
+    import dnrp
+    import lut_cases as LC
+    psd, cfgt = F.CONFIGS[LC.TABLES[table][0]]
+    u_max, b_max, ntx, os_min, L, M = cfgt
+    phy = dnrp.Phy(u_max, b_max, ntx, os_min, L, M, chestim_mode_lr=bool(lr), stride=stride, max_batch=max_batch)
+    for nid in range(100, 106):
+        phy.add_network_id(nid)
+    ps, ops = dnrp.psdef(*psd), O.psdef(*psd)
+    sz = phy.packet_sizes(ps)
+    ws = LC.windows(table)
+    assert ws[0]["win"].shape == (ntx, sz["N_samples_packet_os_rs"])
+    reports = [dnrp.SyncReport(w["fine_peak"], w["cfo_est"], 0.0, ops[0], ops[1], sz["N_eff_TX"]) for w in ws]
+    for rep, w in zip(reports, ws):
+        assert float(np.float32(rep.cfo_fractional_rad)) == w["cfo_est"]
+        if w["sync_rms"] is not None:
+            rep.rms[0] = w["sync_rms"][0]
+    hard = [w["base"] >= 20.0 and w["step"] is None for w in ws]
+    return (phy, ps, ops, [w["win"] for w in ws], reports, [w["nid"] for w in ws], [w["pt"] for w in ws],
+            [w["pdc"] for w in ws], hard, lambda i: LC.oracle(table, i, lr, stride))
+
+
+# id: (table, chestim lr, stride, environment, kernel whose launch count is asserted, launched or not)
+LUT_CASES = {
+    "C4-epoch-lr-s1": ("C4", 1, 1, {"DNRP_RX_EPOCH": "2"}, "rx_epoch", True),
+    "C4-epoch-lr-s2": ("C4", 1, 2, {"DNRP_RX_EPOCH": "2"}, "rx_epoch", True),
+    "C4-epoch-lr-s3": ("C4", 1, 3, {"DNRP_RX_EPOCH": "2"}, "rx_epoch", True),
+    "C4-epoch-l": ("C4", 0, 2, {"DNRP_RX_EPOCH": "2"}, "rx_epoch", True),
+    "C4-default-lr-s2": ("C4", 1, 2, {}, "rx_epoch", True),
+    "C4-ypath-lr-s2": ("C4", 1, 2, {"DNRP_RX_EPOCH": "0"}, "rx_epoch", False),
+    "C4-ypath-l": ("C4", 0, 2, {"DNRP_RX_EPOCH": "0"}, "rx_epoch", False),
+    "C4-fused-lr-s2": ("C4", 1, 2, {"DNRP_RX_FUSED": "1"}, "rx_fused", True),
+    "C3-default-lr-s1": ("C3", 1, 1, {}, "rx_epoch", False),
+    "C3-default-lr-s2": ("C3", 1, 2, {}, "rx_epoch", False),
+    "C3-default-l": ("C3", 0, 2, {}, "rx_epoch", False),
+    "C3-epoch-lr-s2": ("C3", 1, 2, {"DNRP_RX_EPOCH": "2"}, "rx_epoch", True),
+    # the picks made from sums that rx_snr_kernel gathers from Y
+    "C4-snr-from-y-lr-s2": ("C4", 1, 2, {"DNRP_RX_SNR_FRONT": "0"}, "rx_epoch", True),
+}
+_LUT_ENV = ("DNRP_RX_EPOCH", "DNRP_RX_FUSED", "DNRP_RX_SNR_FRONT", "DNRP_RX_GROUP")
+
+
+def _rx_lut_parity(tag, table, lr, stride, env, monkeypatch):
+    for k in _LUT_ENV:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("DNRP_TIMING", "1")  # launch counts: each case proves which kernel ran
+    return _rx_parity("lut:" + tag, stride, _lut_prepared(table, lr, stride))
+
+
+@pytest.mark.parametrize("case", sorted(LUT_CASES))
+def test_rx_lut_profiles(case, monkeypatch):
+    """The bench instantiations (rx_epoch_kernel<4, 4, 8>, rx_cells with NBPS = 8, SISO and 4 x 4) at the
+    -5 dB and 15 dB profiles as well as the 35 dB one, and with the pick changing inside a packet, all in
+    one batch (C4: picks 0, 1, 2, 2 -> 1, 1 -> 0; C3: 0, 1, 2, 2 -> 1), so one launch indexes lut_d by
+    slot and by DRS operation with different values -- every check of _check_rx, through each receiver."""
+    table, lr, stride, env, kernel, ran = LUT_CASES[case]
+    phy = _rx_lut_parity(case, table, lr, stride, env, monkeypatch)
+    count = phy.kernel_time_total(kernel)[1]
+    assert (count > 0) == ran, (case, kernel, count)
+    assert phy.kernel_time_total("rx_pdc_phase")[1] == 0, case
+
+
+def test_rx_llr_clamp(monkeypatch):
+    """LLRs far past the int16 range (C3, 12 dB, a noise step at -8 dB from the middle of the window: SISO
+    zero-forcing of noise-dominated 256-QAM cells): the descrambling sign is applied before the clamp, so
+    full scale keeps the sign of the pre-quantisation value. The oracle quantises and then descrambles with
+    a saturating negation, so the two agree within 1 LSB at the clamp as well.
+    The row is ill-conditioned for float32 (the oracle's own float path leaves its double path by more than
+    1 LSB on a share s_ref of it), so instead of the +-1 gate the share of |GPU - oracle| > 1 is bounded by
+    2 s_ref + 2 / n: two float32 pipelines of equal conditioning in different summation order, on a count
+    that scatters by about its square root; a wrong pick moves 6 % or more
+    (tests/test_rx_lut_inputs.py)."""
+    import json
+    import os
+    import lut_cases as LC
+    for k in _LUT_ENV:
+        monkeypatch.delenv(k, raising=False)
+    phy, ps, ops, windows, reports, nids, types, _, _, oracle = _lut_prepared("C3_clamp")
+    r, rf = oracle(0), LC.oracle("C3_clamp", 0, use_float=True)
+    f, o = r["pdc_llr_f"], r["pdc_llr"].astype(np.int32)
+    pos, neg = f >= 65536, f <= -65536  # twice full scale: no float32 error moves these across the clamp
+    assert np.count_nonzero(pos) >= 16 and np.count_nonzero(neg) >= 16, (np.count_nonzero(pos), np.count_nonzero(neg))
+    g_pcc, g_pdc, rep1, rep2 = _gpu_rx(phy, ps, phy.packet_sizes(ps), windows, reports, nids, types)
+    g = g_pdc[0][: len(o)].astype(np.int32)
+    n = len(o)
+    s_ref = np.count_nonzero(np.abs(rf["pdc_llr"].astype(np.int32) - o) > 1) / n
+    share = np.count_nonzero(np.abs(g - o) > 1) / n
+    wrong = np.flatnonzero((np.abs(f) >= 64) & ((f > 0) != (g > 0)))
+    stats = {"tag": "clamp:C3", "n": n, "share_gt1": share, "s_ref": s_ref, "max": int(np.abs(g - o).max()),
+             "n_pos": int(np.count_nonzero(pos)), "n_neg": int(np.count_nonzero(neg)), "wrong_sign": int(wrong.size)}
+    print(stats)
+    if os.environ.get("DNRP_PARITY_STATS"):
+        with open(os.environ["DNRP_PARITY_STATS"], "a") as fh:
+            fh.write(json.dumps(stats) + "\n")
+    assert np.all(g[pos] == 32767), g[pos][g[pos] != 32767][:8]
+    assert np.all(g[neg] == -32768), g[neg][g[neg] != -32768][:8]
+    assert wrong.size == 0, (wrong[:8].tolist(), f[wrong[:8]].tolist(), g[wrong[:8]].tolist())
+    assert share <= 2 * s_ref + 2 / n, (share, s_ref)
+    # the PCC lies before the step: the gate holds there, and so do the reports
+    llr_gate.check(("clamp:C3", "pcc"), g_pcc[0], r["pcc_llr"])
+    assert abs(rep1[0].snr_dB - r["snr_pcc"]) < 0.05 and abs(rep2[0].snr_dB - r["snr_pdc"]) < 0.05
+
+
+# ---- DNRP_RX_GROUP: the Y path in packet groups on two streams (ctx.cpp: fork / join events)
+def test_rx_group_tail_and_mixed_profiles(monkeypatch):
+    """5 packets in groups of 2, 2 and 1 (a tail group), the lut_cases C4 batch with every profile and both
+    step packets: each group's back end reads its own packets' picks and Y."""
+    phy = _rx_lut_parity("C4-group2", "C4", 1, 2, {"DNRP_RX_EPOCH": "0", "DNRP_RX_GROUP": "2"}, monkeypatch)
+    assert phy.kernel_time_total("rx_pdc_phase")[1] > 0
+    assert phy.kernel_time_total("rx_epoch")[1] == 0
+
+
+def test_rx_group_report_after_join(monkeypatch):
+    """2 RX antennas (the Y path by default), groups of one packet, stride 3, with the MIMO report, which
+    reads Y on the main stream after the join. N_b_DFT_os = 512 here: the grouped phase over the generic
+    FFT front end (rx_fft_kernel), not the streaming wave kernel of the C4 cases."""
+    for k in _LUT_ENV:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("DNRP_RX_GROUP", "1")
+    monkeypatch.setenv("DNRP_TIMING", "1")
+    phy = _rx_parity("tm1_txdiv2", 3)
+    assert phy.kernel_time_total("rx_pdc_phase")[1] > 0
+    assert phy.kernel_time_total("rx_epoch")[1] == 0
+
+
+def test_rx_group_not_above_batch(monkeypatch):
+    """A group size no smaller than the batch (5 packets, groups of 8): one ordinary launch on the main
+    stream, no fork -- and parity."""
+    phy = _rx_lut_parity("C4-group8", "C4", 1, 2, {"DNRP_RX_EPOCH": "0", "DNRP_RX_GROUP": "8"}, monkeypatch)
+    assert phy.kernel_time_total("rx_pdc_phase")[1] == 0
+    assert phy.kernel_time_total("rx_epoch")[1] == 0
