@@ -587,6 +587,22 @@ rx2_tables* get_rx2(dnrp_ctx* ctx, const dnrp_psdef& d, int* err) {
         if (syms.empty()) syms.push_back(0);  // non-empty uploads
         if (dsy.empty()) dsy.push_back(0);
         t->ep_ok = ok && plan.epochs.size() > 0;
+        // the epoch receiver's plan with twin segments (same epochs and cells, so the symbol lists above
+        // hold); rx_cells_kernel keeps the plain plan
+        if (t->ep_ok && ctx->eq_twin) {
+            const auto tplan = geo::build_rx_plan(t->maps, pdc_ops, tm.N_eff_TX, true, true);
+            bool any = false;
+            for (const auto& g : tplan.segs) any = any || g.twin;
+            if (any) {
+                if (!t->eplan.upload(tplan)) {
+                    *err = DNRP_ENOMEM;
+                    return nullptr;
+                }
+                // rx_epoch_kernel packs a twin unit's subcarriers (10 bits each) and symbol (12 bits)
+                t->eplan_ok = t->eplan.cells_ok && tplan.epochs.size() == plan.epochs.size() && t->maps.Nf <= 1024 &&
+                              t->q.N_DF_symb + 1 < (1u << 12);
+            }
+        }
         if (t->ep_ok && (!t->ep_off.upload(off) || !t->ep_sym.upload(syms) || !t->ep_drs.upload(dsy))) {
             *err = DNRP_ENOMEM;
             return nullptr;
@@ -792,6 +808,8 @@ int dnrp_ctx_create(const dnrp_cfg* cfg, dnrp_ctx** out) {
     if (ctx->cfg.chestim_lr_stride == 0) ctx->cfg.chestim_lr_stride = 1;
     const char* tm = std::getenv("DNRP_TIMING");
     ctx->timing = tm && tm[0] == '1';
+    const char* tw = std::getenv("DNRP_EQ_TWIN");
+    ctx->eq_twin = !tw || std::atoi(tw) != 0;
     if (!ctx->pcc_seq.upload(geo::gold_bits_packed(0x44454354u, 200))) return DNRP_ENOMEM;  // pcc_enc.cpp:46,104
     *out = ctx.release();
     return DNRP_OK;
@@ -1270,6 +1288,10 @@ int dnrp_rx_pdc_batch(dnrp_ctx* ctx, uint32_t m, const dnrp_pdc_req* req, const 
                                dev::rx_epoch_lds(ec = cells_args(ctx, t, t2->bplan, ng, gsel, true, t2->q.N_bps,
                                                                  t2->pdc_k.as<uint32_t>(), t2->pdc_sym.as<uint16_t>(),
                                                                  pdc_llr, llr_stride, false)) <= 160 * 1024;
+            if (epoch && t2->eplan_ok) {
+                ec.epochs = t2->eplan.epochs.as<dev::rx_epoch>();
+                ec.segs = t2->eplan.segs.as<dev::rx_seg>();
+            }
             if (epoch) {
                 // DRS pass (the phase's DRS symbols: pilots in Y, SNR sums), the SNR chain's LUT picks,
                 // then one workgroup per (packet, epoch): front end of the epoch's symbols + equaliser

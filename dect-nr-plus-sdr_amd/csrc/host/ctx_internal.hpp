@@ -159,6 +159,8 @@ struct rx2_tables {  // per (psdef): PDC phase
     geo::maps_t maps;
     dbuf pdc_k, pdc_sym;
     rx_plan_dev bplan;  // PDC phase back end
+    rx_plan_dev eplan;  // the same plan with twin segments, the epoch receiver's (eplan_ok; else it takes bplan)
+    bool eplan_ok = false;
     bool sm = false;    // spatial multiplexing (N_SS > 1): MMSE cells kernel
     // MIMO report (estimator_mimo_t): wideband DRS cells, single-stream codebooks
     uint32_t N_TS = 1, ncb_tx = 0, A_tx = 0, ncb_rx = 0, A_rx = 0;
@@ -227,6 +229,8 @@ struct dnrp_ctx {
     // PDC phase through the epoch receiver (kernels/rx_epoch.hip, DNRP_RX_EPOCH): 0 off, 1 where it
     // applies and pays (N_RX >= 4), 2 wherever it applies (tests)
     uint32_t rx_epoch = 1;
+    // twin segments in the epoch receiver's plan (geo::build_rx_plan; DNRP_EQ_TWIN=0 at context creation: off)
+    bool eq_twin = true;
     hipStream_t rx_aux = nullptr;
     hipEvent_t rx_fork = nullptr, rx_join = nullptr;
     uint32_t rx_mode = 0;  // DNRP_RX_MODE_* (dnrp_ctx_set_rx_mode)

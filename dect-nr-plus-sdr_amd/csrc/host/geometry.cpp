@@ -710,7 +710,76 @@ void build_rx_ops(const maps_t& m, uint32_t N_eff_TX, uint32_t N_DF, bool mode_l
     }
 }
 
-rx_plan_t build_rx_plan(const maps_t& m, const std::vector<op_t>& ops, uint32_t NT, bool pair_units) {
+namespace {
+// Twin segments (rx_seg_t::twin): a merged run of PDC symbols shares one interpolation event, so two
+// of its symbols with the same subcarrier list have the same interpolated channel per stream
+// (rx_synced.cpp:1092-1103 interpolates once per event). Each run is cut at its symbol boundaries;
+// neighbours l, l + 1 with equal cell count and kk sequence become one twin segment, the rest stays
+// plain (consecutive plain symbols merged again). A run whose symbols would cut an SFBC pair stays whole.
+void split_twins(const maps_t& m, rx_plan_t& p, bool pairs) {
+    std::vector<rx_seg_t> out;
+    const uint32_t n_sym = static_cast<uint32_t>(m.pdc_sym_off.size()) - 1;
+    for (auto& e : p.epochs) {
+        const uint32_t s0 = static_cast<uint32_t>(out.size());
+        uint32_t units = 0;
+        bool open = false;  // the last segment pushed is a plain piece of the run being cut
+        auto push = [&](rx_seg_t s, bool merge) {
+            const uint32_t n = s.twin ? s.twin : s.j1 - s.j0, u = pairs ? n / 2 : n;
+            if (merge && open && out.back().j1 == s.j0) {
+                out.back().j1 = s.j1;
+            } else {
+                s.u0 = units;
+                out.push_back(s);
+            }
+            open = merge;
+            units += u;
+        };
+        for (uint32_t i = e.seg0; i < e.seg1; ++i) {
+            const rx_seg_t& g = p.segs[i];
+            open = false;
+            struct piece {
+                uint32_t l, c0, c1;
+            };
+            std::vector<piece> ps;
+            bool ok = g.kind == OP_PDC;
+            uint32_t j = g.j0;
+            for (uint32_t l = 0; l < n_sym && ok && j < g.j1; ++l) {
+                const uint32_t c0 = m.pdc_sym_off[l], c1 = m.pdc_sym_off[l + 1];
+                if (c1 <= j || c0 == c1) continue;
+                ok = c0 == j && c1 <= g.j1 && !(pairs && ((c1 - c0) & 1u));
+                ps.push_back({l, c0, c1});
+                j = c1;
+            }
+            if (!ok || j != g.j1) {
+                push(g, false);
+                continue;
+            }
+            for (size_t q = 0; q < ps.size(); ++q) {
+                rx_seg_t s = g;
+                s.l = ps[q].l;
+                s.j0 = ps[q].c0;
+                s.j1 = ps[q].c1;
+                const uint32_t n = s.j1 - s.j0;
+                if (q + 1 < ps.size() && ps[q + 1].l == s.l + 1 && ps[q + 1].c1 - ps[q + 1].c0 == n &&
+                    std::equal(m.pdc_k.begin() + s.j0, m.pdc_k.begin() + s.j1, m.pdc_k.begin() + ps[q + 1].c0)) {
+                    s.j1 = ps[q + 1].c1;
+                    s.twin = n;
+                    push(s, false);
+                    ++q;
+                } else {
+                    push(s, true);
+                }
+            }
+        }
+        e.seg0 = s0;
+        e.seg1 = static_cast<uint32_t>(out.size());
+        e.units = units;
+    }
+    p.segs = std::move(out);
+}
+}  // namespace
+
+rx_plan_t build_rx_plan(const maps_t& m, const std::vector<op_t>& ops, uint32_t NT, bool pair_units, bool twin) {
     rx_plan_t p;
     uint16_t src[4][2];
     for (auto& r : src) r[0] = r[1] = RX_SRC_NONE;
@@ -782,6 +851,7 @@ rx_plan_t build_rx_plan(const maps_t& m, const std::vector<op_t>& ops, uint32_t 
             add(s);
         }
     }
+    if (twin) split_twins(m, p, pairs);
     return p;
 }
 

@@ -121,6 +121,8 @@ struct rx_seg_t {
     uint32_t mode, rel, swap, off;  // event: LUT mode, row, TS swap (0/2), write offsets of the latest DRS
     uint32_t drs_cnt;  // DRS ops processed before the event (selects the LUT profile pick)
     uint32_t u0;       // first work unit (cell or SFBC pair) of the segment within its epoch
+    uint32_t twin;     // 0: plain. n > 0: twin, the cells [j0, j0 + n) of symbol l and [j0 + n, j1) of symbol
+                       // l + 1 on the same subcarriers; one unit covers a cell (pair) of both symbols
 };
 struct rx_epoch_t {
     uint16_t src[4][2];
@@ -132,8 +134,12 @@ struct rx_plan_t {
     std::vector<rx_epoch_t> epochs;
 };
 // pair_units: a work unit is an SFBC pair of cells when N_eff_TX > 1 (transmit diversity); false for
-// spatial multiplexing, whose unit is one cell carrying N_SS symbols
-rx_plan_t build_rx_plan(const maps_t& m, const std::vector<op_t>& ops, uint32_t N_eff_TX, bool pair_units = true);
+// spatial multiplexing, whose unit is one cell carrying N_SS symbols.
+// twin: every merged run of PDC symbols is split into twin segments (two consecutive symbols of one
+// event with the same cell count and subcarrier list: the equaliser interpolates a stream's channel
+// once for both) and plain remainders (DRS- or PCC-bearing symbols, an odd last symbol)
+rx_plan_t build_rx_plan(const maps_t& m, const std::vector<op_t>& ops, uint32_t N_eff_TX, bool pair_units = true,
+                        bool twin = false);
 
 // dnrp_rx_sync_batch's tranche schedule (host/sync.cpp): the step frontiers of one call, the last n_steps
 std::vector<uint32_t> sync_tranches(uint32_t n_steps, uint32_t step, uint32_t stf_len, uint32_t n, uint32_t n_ant);

@@ -236,6 +236,40 @@ int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, floa
                 v.push_back(static_cast<float>(m.pdc_sym_off[l + 1] - m.pdc_sym_off[l]));
                 v.push_back(static_cast<float>(drs));
             }
+        } else if (n == "pdc_cells") {  // (b, N_TS, N_eff_TX, N_DF): per PDC cell in mapping order: symbol, subcarrier index
+            if (n_arg != 4 || a(0) == 0 || a(0) > 16 || a(1) == 0 || a(1) > 8 || a(2) == 0 || a(2) > 8 || a(3) > 1024)
+                return DNRP_EINVAL;
+            const auto m = geo::build_maps(a(0), a(1), a(2), a(3));
+            for (uint32_t l = 0; l <= a(3); ++l)
+                for (uint32_t j = m.pdc_sym_off[l]; j < m.pdc_sym_off[l + 1]; ++j) {
+                    v.push_back(static_cast<float>(l));
+                    v.push_back(static_cast<float>(m.pdc_k[j]));
+                }
+        } else if (n == "rx_plan_segs" || n == "rx_plan_epochs") {
+            // (b, N_TS, N_eff_TX, N_DF, mode_lr, stride, twin): the PDC phase's back-end plan
+            // (geo::build_rx_plan) of a transmit-diversity or single-stream packet. rx_plan_segs: per
+            // segment epoch, kind, l, j0, j1, mode, rel, swap, off, drs_cnt, u0, twin; rx_plan_epochs:
+            // per epoch seg0, seg1, units
+            if (n_arg != 7 || a(0) == 0 || a(0) > 16 || a(1) == 0 || a(1) > 8 || a(2) == 0 || a(2) > 8 || a(3) == 0 ||
+                a(3) > 1024 || a(5) == 0)
+                return DNRP_EINVAL;
+            const auto m = geo::build_maps(a(0), a(1), a(2), a(3));
+            std::vector<geo::op_t> pcc_ops, pdc_ops;
+            uint32_t pm = 0;
+            geo::build_rx_ops(m, a(2), a(3), a(4) != 0, a(5), pcc_ops, pdc_ops, pm);
+            const auto p = geo::build_rx_plan(m, pdc_ops, a(2), true, a(6) != 0);
+            for (uint32_t e = 0; e < p.epochs.size(); ++e) {
+                const auto& E = p.epochs[e];
+                if (n == "rx_plan_epochs") {
+                    for (const uint32_t x : {E.seg0, E.seg1, E.units}) v.push_back(static_cast<float>(x));
+                    continue;
+                }
+                for (uint32_t i = E.seg0; i < E.seg1; ++i) {
+                    const auto& s = p.segs[i];
+                    for (const uint32_t x : {e, s.kind, s.l, s.j0, s.j1, s.mode, s.rel, s.swap, s.off, s.drs_cnt, s.u0, s.twin})
+                        v.push_back(static_cast<float>(x));
+                }
+            }
         } else {
             return DNRP_EINVAL;
         }

@@ -164,7 +164,7 @@ constexpr uint32_t RX_MAX_DOPS = 64;  // DRS ops per phase; lut_d holds RX_MAX_D
 
 // back end, see geometry.hpp rx_plan_t (identical layouts)
 struct rx_seg {
-    uint32_t kind, l, j0, j1, mode, rel, swap, off, drs_cnt, u0;
+    uint32_t kind, l, j0, j1, mode, rel, swap, off, drs_cnt, u0, twin;
 };
 struct rx_epoch {
     uint16_t src[4][2];
@@ -256,7 +256,8 @@ struct cell_seg {
     uint32_t u0, j0, l;
     uint32_t info;       // mode | swap << 1 | off << 4 | nI << 12
     const uint32_t* pw;  // LT.pw + rel * 4 * Nf
-    uint32_t wbase, pad;
+    uint32_t wbase;
+    uint32_t twin;       // cells per symbol of a twin segment (rx_seg_t::twin), 0: plain
 };
 
 // LDS bytes of one rx_cells workgroup: pilot buffer, the weight-table slots of mode l and lr,

@@ -212,7 +212,7 @@ __global__ void __launch_bounds__(CELL_THREADS) rx_cells_kernel(rx_cells_args A)
             c.info = (S.mode & 1u) | (S.swap & 3u) << 1 | (S.off & 0xFFu) << 4 | LT.n << 12;
             c.pw = LT.pw + size_t(S.rel) * 4 * (A.N_occ + 1);
             c.wbase = (S.mode & 1u) * A.wcap[0];
-            c.pad = 0;
+            c.twin = 0;
             sg[tid] = c;
         }
         if (tid < 12) pairs[tid] = A.pair[tid];

@@ -12,6 +12,15 @@
 //      pilot buffer and Wiener tables in LDS aliased over the front end's wave regions, Wiener
 //      interpolation, MRC / SFBC combining, int16 demap, descramble) from those rows, which it wrote
 //      microseconds earlier: the reads are served by the L2 / Infinity Cache instead of HBM.
+// The equaliser's work unit is a cell (MRC) or an SFBC pair of one symbol, or -- in a twin segment of
+// the plan (geometry.cpp split_twins: two consecutive symbols of one interpolation event with their
+// PDC cells on the same subcarriers) -- that cell or pair in both symbols. The LUT words, weight rows
+// and pilot buffer of a stream are the same for both symbols, so its interpolated channel is too: a
+// twin unit resolves its subcarriers once, interpolates every distinct stream of its two pairs once
+// (3 instead of 4 with N_TS = 4, where the pair cycle of 6 advances by 4 mod 6 per full symbol; 2
+// instead of 4 with N_TS = 2; 1 instead of 2 for MRC) and combines and emits symbol l, then l + 1; the
+// second symbol's cells are the pipeline's next stage-B load. Same sums in the same order as two
+// plain units: the LLRs do not change (DNRP_EQ_TWIN=0 selects the plan without twins).
 // Symbols of the phase read by no epoch's cells, and the DRS symbols (their pilots and SNR sums feed
 // the SNR chain's LUT picks of every later epoch, rx_synced.cpp:863-891), run before in the DRS pass
 // (rx_fft_wave_ct_kernel on the symbol list, then rx_snr_kernel). Every front-end symbol belongs to
@@ -124,7 +133,7 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
         pc.info = (Sg.mode & 1u) | (Sg.swap & 3u) << 1 | (Sg.off & 0xFFu) << 4 | LT.n << 12;
         pc.pw = LT.pw + size_t(Sg.rel) * 4 * (A.N_occ + 1);
         pc.wbase = (Sg.mode & 1u) * A.wcap[0];
-        pc.pad = 0;
+        pc.twin = Sg.twin;
     }
     __syncthreads();  // the epoch's rows written (workgroup-scope release / acquire), LDS free again
     if constexpr (experiment(XS_EP_SKIP_EQ)) return;
@@ -153,7 +162,7 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
             c.info = (Sg.mode & 1u) | (Sg.swap & 3u) << 1 | (Sg.off & 0xFFu) << 4 | LT.n << 12;
             c.pw = LT.pw + size_t(Sg.rel) * 4 * (A.N_occ + 1);
             c.wbase = (Sg.mode & 1u) * A.wcap[0];
-            c.pad = 0;
+            c.twin = Sg.twin;
             sg[tid] = c;
         }
         if (tid < 12) pairs[tid] = A.pair[tid];
@@ -166,24 +175,68 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
     if constexpr (experiment(XS_EP_SLOTY)) Yp = A.Y + size_t(blockIdx.x % (64u * A.n_epochs)) * NRX * A.n_sym_total * A.Nf_pad;
     __syncthreads();
     if (tid >= units) return;
-    const uint8_t* __restrict__ seq = A.pdc_seq[row];
+    // the row's scrambling sequence: a uniform pointer kept in scalar registers
+    const uintptr_t seqv = reinterpret_cast<uintptr_t>(A.pdc_seq[row]);
+    const uint32_t seq_lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(seqv));  // (the builtin returns int:
+    const uint32_t seq_hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(seqv >> 32));  // no sign extension)
+    const uint8_t* __restrict__ seq = reinterpret_cast<const uint8_t*>(uintptr_t(seq_lo) | uintptr_t(seq_hi) << 32);
     int16_t* __restrict__ llr = A.llr + size_t(row) * A.llr_stride;
     constexpr uint32_t per_unit = NT == 1 ? 1u : 2u;
-    // stage A two units ahead, stage B one unit ahead of eq_compute (rx_eq.hpp)
+    // Stage A two units ahead, stage B one step ahead of the equaliser (rx_eq.hpp). A plain unit is one
+    // step. A twin unit (cell_seg::twin: the same subcarriers in symbols l and l + 1 of one event) is
+    // two: its stage A serves both symbols, the second symbol's cells and scrambling bytes are the stage
+    // B in flight during the first symbol's step (never two symbols' cells at once), and its second step
+    // reuses the first one's interpolated channels (eq_interp_second). The workgroup's threads stay on the
+    // same unit round: in a wavefront that mixes plain and twin units the plain lanes idle through the
+    // second step.
     uint32_t si = 0;
     unit_a na;
     unit_b<NRX, NT> cur;
     uint32_t u = tid;
+    const uint32_t N_bps = NBPS ? static_cast<uint32_t>(NBPS) : A.N_bps;
+    // the current unit's subcarriers and symbol (a twin unit's second stage B) in one register: 10 bits
+    // per subcarrier index (N_b_DFT_os = 1024), 12 for the symbol (host-checked where the plan has twins)
+    auto pack_a = [](const unit_a& a) { return a.k0 | a.k1 << 10 | a.l << 20; };
     unit_stage_a(A, sg, nseg, si, u, per_unit, na);
     unit_stage_b<NRX, NT>(A, sg, pairs, Yp, seq, na, cur);
+    uint32_t ca = pack_a(na);
     if (u + EP_THREADS < units) unit_stage_a(A, sg, nseg, si, u + EP_THREADS, per_unit, na);
+    unit_merge_bits<NRX, NT>(N_bps, cur);
     for (; u < units; u += EP_THREADS) {
-        unit_b<NRX, NT> nb;
         const bool m1 = u + EP_THREADS < units, m2 = u + 2 * EP_THREADS < units;
-        if (m1) unit_stage_b<NRX, NT>(A, sg, pairs, Yp, seq, na, nb);
-        if (m2) unit_stage_a(A, sg, nseg, si, u + 2 * EP_THREADS, per_unit, na);
-        eq_compute<NRX, NT, NBPS>(A, sg, zfi, wtab, zst, cur, llr);
-        if (m1) cur = nb;
+        const uint32_t tw = sg[cur.si()].twin, steps = tw ? 2u : 1u;
+        float2 g0[NRX], g1[NRX];
+        uint32_t ptab = 0;
+#pragma unroll 1
+        for (uint32_t h = 0; h < steps; ++h) {
+            const bool last = h + 1 == steps;
+            unit_b<NRX, NT> nb;
+            unit_a sa = na;  // the next step's stage B: the next unit, or this unit one symbol on
+            if (!last) {
+                sa.si = cur.si();
+                sa.jj = cur.jj + tw;
+                sa.k0 = ca & 0x3FFu;
+                sa.k1 = (ca >> 10) & 0x3FFu;
+                sa.l = (ca >> 20) + 1;
+            }
+            const bool more = !last || m1;
+            if (more) unit_stage_b<NRX, NT>(A, sg, pairs, Yp, seq, sa, nb);
+            if (last) {
+                ca = pack_a(na);
+                if (m2) unit_stage_a(A, sg, nseg, si, u + 2 * EP_THREADS, per_unit, na);
+            }
+            if (h == 0) {
+                eq_interp_first<NRX, NT>(sg, zfi, wtab, zst, cur, g0, g1);
+                ptab = cur.tab();
+            } else {
+                eq_interp_second<NRX, NT>(sg, zfi, wtab, zst, cur, ptab, g0, g1);
+            }
+            eq_emit<NRX, NT, NBPS>(A, cur, g0, g1, llr);
+            if (more) {
+                cur = nb;
+                unit_merge_bits<NRX, NT>(N_bps, cur);
+            }
+        }
     }
 }
 

@@ -13,6 +13,9 @@ namespace dnrp::dev {
 #ifndef DNRP_CELLS_CH
 #define DNRP_CELLS_CH 3  // SFBC interpolation taps per chunk (eq_compute): 3 keeps rx_cells<4, 4> at 121 VGPRs (4: 131, one workgroup per CU)
 #endif
+#ifndef DNRP_CELLS_CH1
+#define DNRP_CELLS_CH1 2  // taps per chunk of a single stream's interpolation (eq_interp_one)
+#endif
 
 // the pilot-buffer layout of rx_cells_kernel<NRX, NT, SM>: antenna pairs interleaved for the MMSE
 // path and for SFBC with an even antenna count (build_pilots)
@@ -88,9 +91,11 @@ struct unit_a {
 template <int NRX, int NT>
 struct unit_b {
     static constexpr int NC = NT == 1 ? 1 : 4;  // interpolated channels per unit
-    uint32_t si, jj, tab;                       // tab: tA | tB << 4
+    uint32_t sit, jj;                           // sit: segment | tab << 8, tab: tA | tB << 4
     uint32_t pw[NC];
-    uint32_t sb[3];                             // scrambling bytes from bit (jj N_bps) & ~7 (raw loads)
+    uint32_t sb[3];                             // scrambling bytes from bit (jj N_bps) & ~7 (raw loads; merged: sb[0], unit_merge_bits)
+    __device__ __forceinline__ uint32_t si() const { return sit & 0xFFu; }
+    __device__ __forceinline__ uint32_t tab() const { return sit >> 8; }
     float2 r0[NRX], r1[NT == 1 ? 1 : NRX];
 };
 
@@ -120,15 +125,14 @@ __device__ __forceinline__ void unit_stage_b(const rx_cells_args& A, const cell_
     const uint32_t swap = (S.info >> 1) & 3u;
     const auto spw = as_global(S.pw);
     const auto sq = as_global(seq);
-    b.si = a.si;
     b.jj = a.jj;
     if constexpr (NT == 1) {
-        b.tab = 0;
+        b.sit = a.si;
         b.pw[0] = spw[swap * Nf + a.k0];
     } else {
         const uint32_t pr = pairs[(a.jj >> 1) % A.mod];
         const uint32_t tA = pr & 0xFu, tB = pr >> 4;
-        b.tab = tA | tB << 4;
+        b.sit = a.si | pr << 8;
         b.pw[0] = spw[((tA & 3u) ^ swap) * Nf + a.k0];
         b.pw[1] = spw[((tA & 3u) ^ swap) * Nf + a.k1];
         b.pw[2] = spw[((tB & 3u) ^ swap) * Nf + a.k0];
@@ -196,141 +200,287 @@ __device__ __forceinline__ void emit_cell(float2 x, uint32_t j, uint32_t j0, uin
         if (b < N_bps) llr[base + b] = q16(sbit(b) ? -L[b] : L[b]);
 }
 
-// Wiener interpolation (rx_synced.cpp:893-949), MRC (1204-1306) or SFBC combining (1335-1392),
-// demapping and the LLR store of one unit. zfi: the epoch's pilot rows [NRX][NT][zst]; wtab: the
-// weight-table slots.
+// ---- the equaliser of one unit in steps: the segment's event, the LDS addresses of an interpolation,
+// the interpolation of one stream (MRC: at the cell; SFBC: the mean over the pair's union window), and
+// combine + demap + LLR store. eq_compute chains them for a plain unit; a twin unit (cell_seg::twin:
+// the same subcarriers in symbols l and l + 1 of one event) interpolates each distinct stream once and
+// combines twice (eq_interp_first, eq_interp_second, eq_emit after each).
+struct eq_ev {
+    uint32_t mode, off, nI, wbase;
+};
+__device__ __forceinline__ eq_ev eq_event(const cell_seg& S) {
+    const uint32_t info = S.info;
+    return {info & 1u, (info >> 4) & 0xFFu, info >> 12, S.wbase};
+}
+
+// the unit's scrambling bits from bit (jj N_bps) & ~7 (unit_stage_b's raw byte loads)
+template <int NT>
+__device__ __forceinline__ uint32_t unit_bits(uint32_t jj, uint32_t N_bps, const uint32_t (&sb)[3]) {
+    const uint32_t b0 = (jj * N_bps) >> 3, bl = ((jj + (NT == 1 ? 1u : 2u)) * N_bps - 1) >> 3;
+    return sb[0] | (b0 + 1 <= bl ? sb[1] << 8 : 0u) | (b0 + 2 <= bl ? sb[2] << 16 : 0u);
+}
+// the same word left in sb[0] (sb[1], sb[2] zero: unit_bits returns it unchanged), once the loads have
+// landed: two registers fewer while the unit waits for its step
+template <int NRX, int NT>
+__device__ __forceinline__ void unit_merge_bits(uint32_t N_bps, unit_b<NRX, NT>& b) {
+    b.sb[0] = unit_bits<NT>(b.jj, N_bps, b.sb);
+    b.sb[1] = b.sb[2] = 0u;
+}
+
+// pilot start (LDS float2 index) and weight offset (LDS float index) of stream t's interpolation at
+// the subcarrier of LUT word pw. SFBC with an even antenna count reads the antenna-pair-interleaved
+// pilot buffer (AI, see build_pilots): positions in float2 of the stream's first pair row, pilot
+// steps of 2 float2
+template <int NRX, int NT>
+__device__ __forceinline__ void eq_addr(const eq_ev& E, uint32_t zst, uint32_t pw, uint32_t t, uint32_t& pos, uint32_t& wo) {
+    constexpr bool AI = cells_ai(NRX, NT);
+    uint32_t p = pw & 0xFFFFu;
+    if (!E.mode) p = 2 * p + ((E.off >> t) & 1u);  // non-interlaced: latest DRS symbol only
+    if (experiment(XS_CELLS_ONE_PILOT)) p = 0;
+    pos = AI ? ((experiment(XS_CELLS_ONE_ROW) ? 0u : t * (NRX / 2) * zst) + p) * 2
+             : p + (experiment(XS_CELLS_ONE_ROW) ? 0u : t * zst);
+    wo = E.wbase + (experiment(XS_CELLS_ONE_WROW) ? 0u : (pw >> 16) * E.nI);
+}
+
+// MRC: the channel of every antenna at one cell (rx_synced.cpp:932-946)
+template <int NRX, int NT>
+__device__ __forceinline__ void eq_interp_cell(const eq_ev& E, const float2* zfi, const float* wtab, uint32_t zst,
+                                               uint32_t pos, uint32_t wo, float2 (&h)[NRX]) {
+    const uint32_t nI = E.nI, step = E.mode ? 1u : 2u;
+#pragma unroll
+    for (int a = 0; a < NRX; ++a) h[a] = make_float2(0.f, 0.f);
+    // taps in chunks of CH, the chunk's reads issued before its FMAs; taps past nI read the last
+    // one with weight 0 (exact zeros: the tap-ordered sums of the one-tap loop, bit for bit)
+    constexpr uint32_t CH = 4;
+    for (uint32_t i0 = 0; i0 < nI; i0 += CH) {
+        float wv[CH];
+        float2 z[CH][NRX];
+#pragma unroll
+        for (uint32_t j = 0; j < CH; ++j) {
+            const uint32_t i = min(i0 + j, nI - 1);
+            const float w = wtab[wo + i];
+            wv[j] = i0 + j < nI ? w : 0.f;
+#pragma unroll
+            for (int a = 0; a < NRX; ++a) z[j][a] = zfi[a * NT * zst + pos + i * step];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < CH; ++j)
+#pragma unroll
+            for (int a = 0; a < NRX; ++a) {
+                h[a].x = fmaf(z[j][a].x, wv[j], h[a].x);
+                h[a].y = fmaf(z[j][a].y, wv[j], h[a].y);
+            }
+    }
+}
+
+// MRC (rx_synced.cpp:1204-1306), demapping and the LLR store of cell b.jj
+template <int NRX, int NT, int NBPS>
+__device__ __forceinline__ void eq_emit_mrc(const rx_cells_args& A, const unit_b<NRX, NT>& b, const float2 (&h)[NRX],
+                                            int16_t* __restrict__ llr) {
+    const uint32_t N_bps = NBPS ? static_cast<uint32_t>(NBPS) : A.N_bps;
+    const uint32_t bits = unit_bits<NT>(b.jj, N_bps, b.sb);
+    float2 num = make_float2(0.f, 0.f);
+    float den = 0.f;
+#pragma unroll
+    for (int a = 0; a < NRX; ++a) {
+        num = cadd(num, cmulc(b.r0[a], h[a]));
+        den += cnorm(h[a]);
+    }
+    emit_cell(cscale(num, 1.0f / den), b.jj, b.jj, N_bps, bits, llr);
+}
+
+// SFBC: a stream's pair channel is the mean of its interpolations at k0 and k1
+// (rx_synced.cpp:1365-1371). Both read the stream's pilot row with windows sh pilots apart
+// (0 or 1 almost everywhere): one pass over the union window of nI + sh taps with the mean
+// weights gives the mean with about half the pilot reads and FMAs of two passes.
+struct eq_win {
+    uint32_t base, sh, wl, wh;  // first pilot, window distance in pilots, weight offsets of the lower / upper window
+};
+template <int NRX, int NT>
+__device__ __forceinline__ eq_win eq_window(const eq_ev& E, uint32_t zst, uint32_t pw0, uint32_t pw1, uint32_t t) {
+    constexpr uint32_t PS = cells_ai(NRX, NT) ? 2u : 1u;
+    const uint32_t step = E.mode ? 1u : 2u;
+    uint32_t p0, p1, w0, w1;
+    eq_addr<NRX, NT>(E, zst, pw0, t, p0, w0);
+    eq_addr<NRX, NT>(E, zst, pw1, t, p1, w1);
+    const bool up = p1 >= p0;
+    return {up ? p0 : p1, (up ? p1 - p0 : p0 - p1) / (PS * step), up ? w0 : w1, up ? w1 : w0};
+}
+
+// One chunk of CH taps from tap i0 of a stream's union window, for every antenna: every LDS read of
+// the chunk (weights at clamped indices, pilots) issued before its FMAs: one LDS latency per chunk
+// instead of per tap, no exec-mask branches. Taps past the union window carry weight 0 (their read
+// stays in the row + ZFI_PAD) and add exact zeros, so the per-antenna sums are the tap-ordered sums
+// of the one-tap loop, bit for bit, however many chunks run.
+template <int NRX, int NT, uint32_t CH = DNRP_CELLS_CH>
+__device__ __forceinline__ void eq_win_chunk(const eq_ev& E, const float2* zfi, const float* wtab, uint32_t zst,
+                                             const eq_win& W, uint32_t i0, float2 (&g)[NRX]) {
+    constexpr bool AI = cells_ai(NRX, NT);
+    const uint32_t nI = E.nI;
+    const uint32_t psh = (AI ? 1u : 0u) + (E.mode ? 0u : 1u);  // log2(PS * step): a shift, not v_mul_lo
+    float wv[CH];
+    float2 z[CH][NRX];
+#pragma unroll
+    for (uint32_t j = 0; j < CH; ++j) {
+        const uint32_t i = i0 + j, ih = i - W.sh;  // ih wraps for i < sh
+        const float lo = wtab[W.wl + min(i, nI - 1)], hi = wtab[W.wh + min(ih, nI - 1)];
+        wv[j] = 0.5f * ((i < nI ? lo : 0.f) + (ih < nI ? hi : 0.f));
+        const uint32_t p = W.base + (min(i, nI + W.sh) << psh);
+        if constexpr (AI) {
+            typedef float f4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+            for (int q = 0; q < NRX / 2; ++q) {
+                const f4 v = *reinterpret_cast<const f4*>(zfi + p + q * zst * 2);
+                z[j][2 * q] = make_float2(v.x, v.y);
+                z[j][2 * q + 1] = make_float2(v.z, v.w);
+            }
+        } else {
+#pragma unroll
+            for (int a = 0; a < NRX; ++a) z[j][a] = zfi[a * NT * zst + p];
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < CH; ++j)
+#pragma unroll
+        for (int a = 0; a < NRX; ++a) {
+            g[a].x = fmaf(z[j][a].x, wv[j], g[a].x);
+            g[a].y = fmaf(z[j][a].y, wv[j], g[a].y);
+        }
+}
+
+// the two streams of a pair, chunks alternating (one stream's chunk live at a time)
+template <int NRX, int NT>
+__device__ __forceinline__ void eq_interp_pair(const eq_ev& E, const float2* zfi, const float* wtab, uint32_t zst,
+                                               const uint32_t (&pw)[4], uint32_t tab, float2 (&g0)[NRX], float2 (&g1)[NRX]) {
+    const eq_win W0 = eq_window<NRX, NT>(E, zst, pw[0], pw[1], tab & 0xFu);
+    const eq_win W1 = eq_window<NRX, NT>(E, zst, pw[2], pw[3], tab >> 4);
+    const uint32_t ntap = E.nI + max(W0.sh, W1.sh);
+#pragma unroll
+    for (int a = 0; a < NRX; ++a) g0[a] = g1[a] = make_float2(0.f, 0.f);
+    for (uint32_t i0 = 0; i0 < ntap; i0 += DNRP_CELLS_CH) {
+        __builtin_amdgcn_sched_barrier(0);
+        eq_win_chunk<NRX, NT>(E, zfi, wtab, zst, W0, i0, g0);
+        __builtin_amdgcn_sched_barrier(0);
+        eq_win_chunk<NRX, NT>(E, zfi, wtab, zst, W1, i0, g1);
+    }
+}
+
+// one stream alone: the same per-antenna sums as its half of eq_interp_pair (the chunks past its own
+// union window add exact zeros there). Chunks of DNRP_CELLS_CH1 taps: the twin unit's second symbol
+// holds both of its channels beside the chunk, and 2 covers the 3 or 4 taps of the 35 dB profile's
+// union window in the same two chunks as 3 would
+template <int NRX, int NT>
+__device__ __forceinline__ void eq_interp_one(const eq_ev& E, const float2* zfi, const float* wtab, uint32_t zst,
+                                              const eq_win& W, float2 (&g)[NRX]) {
+    const uint32_t ntap = E.nI + W.sh;
+    for (uint32_t i0 = 0; i0 < ntap; i0 += DNRP_CELLS_CH1) {
+        __builtin_amdgcn_sched_barrier(0);
+        eq_win_chunk<NRX, NT, DNRP_CELLS_CH1>(E, zfi, wtab, zst, W, i0, g);
+    }
+}
+
+// SFBC pair combining (rx_synced.cpp:1373-1391) with the channels h0 / h1 of the pair's first / second
+// stream, demapping and the LLR stores of cells b.jj, b.jj + 1
+template <int NRX, int NT, int NBPS>
+__device__ __forceinline__ void eq_emit_sfbc(const rx_cells_args& A, const unit_b<NRX, NT>& b, const float2 (&g0)[NRX],
+                                             const float2 (&g1)[NRX], int16_t* __restrict__ llr) {
+    const uint32_t N_bps = NBPS ? static_cast<uint32_t>(NBPS) : A.N_bps;
+    const uint32_t bits = unit_bits<NT>(b.jj, N_bps, b.sb);
+    float2 n0 = make_float2(0.f, 0.f), n1 = make_float2(0.f, 0.f);
+    float den = 0.f;
+#pragma unroll
+    for (int a = 0; a < NRX; ++a) {
+        const float2 h0 = g0[a], h1 = g1[a];
+        n0 = cadd(n0, cadd(cmul(cconj(h0), b.r0[a]), cmul(h1, cconj(b.r1[a]))));
+        n1 = cadd(n1, cadd(cmul(make_float2(-h1.x, -h1.y), cconj(b.r0[a])), cmul(cconj(h0), b.r1[a])));
+        den += cnorm(h0) + cnorm(h1);
+    }
+    emit_cell(cscale(n0, 1.0f / den), b.jj, b.jj, N_bps, bits, llr);
+    emit_cell(cscale(n1, 1.0f / den), b.jj + 1, b.jj, N_bps, bits, llr);
+}
+
+// MRC or SFBC combining, demapping and the LLR store of a unit with the interpolated channels g0 (MRC:
+// the cell's; SFBC: the pair's first stream, tab & 15) and g1 (SFBC: the second stream, tab >> 4).
+// The epoch receiver calls it at one place for plain units and both symbols of a twin unit: one
+// instruction sequence, so equal channels give equal LLRs whatever the compiler contracts.
 // NBPS: bits per cell fixed at compile time (8: 256-QAM, the bench's C3 / C4), 0: A.N_bps at run time
+template <int NRX, int NT, int NBPS = 0>
+__device__ __forceinline__ void eq_emit(const rx_cells_args& A, const unit_b<NRX, NT>& b, const float2 (&g0)[NRX],
+                                        const float2 (&g1)[NRX], int16_t* __restrict__ llr) {
+    if constexpr (NT == 1)
+        eq_emit_mrc<NRX, NT, NBPS>(A, b, g0, llr);
+    else
+        eq_emit_sfbc<NRX, NT, NBPS>(A, b, g0, g1, llr);
+}
+
+// A unit's first (or only) symbol: Wiener interpolation (rx_synced.cpp:893-949) of its channels into g0
+// and g1 (see eq_emit). zfi: the epoch's pilot rows [NRX][NT][zst]; wtab: the weight-table slots.
+template <int NRX, int NT>
+__device__ __forceinline__ void eq_interp_first(const cell_seg* sg, const float2* zfi, const float* wtab, uint32_t zst,
+                                                const unit_b<NRX, NT>& b, float2 (&g0)[NRX], float2 (&g1)[NRX]) {
+    const eq_ev E = eq_event(sg[b.si()]);
+    if constexpr (NT == 1) {
+        uint32_t pos, wo;
+        eq_addr<NRX, NT>(E, zst, b.pw[0], 0, pos, wo);
+        eq_interp_cell<NRX, NT>(E, zfi, wtab, zst, pos, wo, g0);
+    } else {
+        eq_interp_pair<NRX, NT>(E, zfi, wtab, zst, b.pw, b.tab(), g0, g1);
+    }
+}
+
+// A twin unit's second symbol: g0, g1 hold the first symbol's channels and leave with this symbol's; b
+// is its stage-B loads at the same subcarriers one symbol on. The event, LUT words, weights and pilots
+// are the first symbol's, so a stream of both pairs has the same channel, bit for bit. Only the streams
+// the first pair (ptab) did not carry are interpolated -- one of two with N_TS = 4 (which one differs
+// from lane to lane: it goes through one single-stream loop, the lane's kept channel selected beside
+// it), none with N_TS = 2 and MRC.
+template <int NRX, int NT>
+__device__ __forceinline__ void eq_interp_second(const cell_seg* sg, const float2* zfi, const float* wtab, uint32_t zst,
+                                                 const unit_b<NRX, NT>& b, uint32_t ptab, float2 (&g0)[NRX],
+                                                 float2 (&g1)[NRX]) {
+    if constexpr (NT > 1) {
+        const eq_ev E = eq_event(sg[b.si()]);
+        const uint32_t pA = ptab & 0xFu, pB = ptab >> 4, tA = b.tab() & 0xFu, tB = b.tab() >> 4;
+        const bool need0 = tA != pA && tA != pB, need1 = tB != pA && tB != pB;
+        // K: the channel kept, N: the one interpolated where any is missing. Only the pair's first stream
+        // missing (f): K is the second stream's; else K is the first stream's (interpolated too in the
+        // rare case that both are missing). K moves to g0 and N to g1 by swaps in place: no second copy of
+        // the channels is ever live
+        const bool f = need0 && !need1;
+        const uint32_t tK = f ? tB : tA, tN = f ? tA : tB;
+        auto swap_if = [&](bool c) {
+#pragma unroll
+            for (int a = 0; a < NRX; ++a) {
+                const float2 t = g0[a];
+                g0[a] = c ? g1[a] : t;
+                g1[a] = c ? t : g1[a];
+            }
+        };
+        swap_if(tK == pB);  // a kept K is the first pair's stream pA (in g0) or pB (in g1); a kept N is the other one
+        if (need0 || need1) {
+            const eq_win W = eq_window<NRX, NT>(E, zst, f ? b.pw[0] : b.pw[2], f ? b.pw[1] : b.pw[3], tN);
+#pragma unroll
+            for (int a = 0; a < NRX; ++a) g1[a] = make_float2(0.f, 0.f);
+            eq_interp_one<NRX, NT>(E, zfi, wtab, zst, W, g1);
+        }
+        if (need0 && need1) {
+            const eq_win W = eq_window<NRX, NT>(E, zst, b.pw[0], b.pw[1], tK);
+#pragma unroll
+            for (int a = 0; a < NRX; ++a) g0[a] = make_float2(0.f, 0.f);
+            eq_interp_one<NRX, NT>(E, zfi, wtab, zst, W, g0);
+        }
+        swap_if(f);  // g0: the pair's first stream, g1: its second
+    }
+}
+
+// a plain unit
 template <int NRX, int NT, int NBPS = 0>
 __device__ __forceinline__ void eq_compute(const rx_cells_args& A, const cell_seg* sg, const float2* zfi,
                                            const float* wtab, uint32_t zst, const unit_b<NRX, NT>& b,
                                            int16_t* __restrict__ llr) {
-    constexpr int NC = unit_b<NRX, NT>::NC;
-    const uint32_t N_bps = NBPS ? static_cast<uint32_t>(NBPS) : A.N_bps;
-    const uint32_t b0 = (b.jj * N_bps) >> 3, bl = ((b.jj + (NT == 1 ? 1u : 2u)) * N_bps - 1) >> 3;
-    const uint32_t bits = b.sb[0] | (b0 + 1 <= bl ? b.sb[1] << 8 : 0u) | (b0 + 2 <= bl ? b.sb[2] << 16 : 0u);
-    const uint32_t info = sg[b.si].info, wbase = sg[b.si].wbase;
-    const uint32_t mode = info & 1u, off = (info >> 4) & 0xFFu, nI = info >> 12;
-    const uint32_t step = mode ? 1u : 2u;
-    // SFBC with an even antenna count reads the antenna-pair-interleaved pilot buffer (AI, see
-    // build_pilots): positions in float2 of the stream's first pair row, pilot steps of 2 float2
-    constexpr bool AI = cells_ai(NRX, NT);
-    constexpr uint32_t PS = AI ? 2u : 1u;
-    uint32_t pos[NC], wo[NC];  // pilot start (LDS float2 index) and weight offset (LDS float index)
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const uint32_t t = c < 2 ? (b.tab & 0xFu) : (b.tab >> 4);
-        uint32_t p = b.pw[c] & 0xFFFFu;
-        if (!mode) p = 2 * p + ((off >> t) & 1u);  // non-interlaced: latest DRS symbol only
-        if (experiment(XS_CELLS_ONE_PILOT)) p = 0;
-        pos[c] = AI ? ((experiment(XS_CELLS_ONE_ROW) ? 0u : t * (NRX / 2) * zst) + p) * 2
-                    : p + (experiment(XS_CELLS_ONE_ROW) ? 0u : t * zst);
-        wo[c] = wbase + (experiment(XS_CELLS_ONE_WROW) ? 0u : (b.pw[c] >> 16) * nI);
-    }
-    if constexpr (NT == 1) {
-        float2 h[NRX];
-#pragma unroll
-        for (int a = 0; a < NRX; ++a) h[a] = make_float2(0.f, 0.f);
-        // taps in chunks of CH, the chunk's reads issued before its FMAs; taps past nI read the last
-        // one with weight 0 (exact zeros: the tap-ordered sums of the one-tap loop, bit for bit)
-        constexpr uint32_t CH = 4;
-        for (uint32_t i0 = 0; i0 < nI; i0 += CH) {
-            float wv[CH];
-            float2 z[CH][NRX];
-#pragma unroll
-            for (uint32_t j = 0; j < CH; ++j) {
-                const uint32_t i = min(i0 + j, nI - 1);
-                const float w = wtab[wo[0] + i];
-                wv[j] = i0 + j < nI ? w : 0.f;
-#pragma unroll
-                for (int a = 0; a < NRX; ++a) z[j][a] = zfi[a * NT * zst + pos[0] + i * step];
-            }
-#pragma unroll
-            for (uint32_t j = 0; j < CH; ++j)
-#pragma unroll
-                for (int a = 0; a < NRX; ++a) {
-                    h[a].x = fmaf(z[j][a].x, wv[j], h[a].x);
-                    h[a].y = fmaf(z[j][a].y, wv[j], h[a].y);
-                }
-        }
-        float2 num = make_float2(0.f, 0.f);
-        float den = 0.f;
-#pragma unroll
-        for (int a = 0; a < NRX; ++a) {  // MRC (rx_synced.cpp:1204-1306)
-            num = cadd(num, cmulc(b.r0[a], h[a]));
-            den += cnorm(h[a]);
-        }
-        emit_cell(cscale(num, 1.0f / den), b.jj, b.jj, N_bps, bits, llr);
-    } else {
-        // SFBC: a stream's pair channel is the mean of its interpolations at k0 and k1
-        // (rx_synced.cpp:1365-1371). Both read the stream's pilot row with windows sh pilots apart
-        // (0 or 1 almost everywhere): one pass over the union window of nI + sh taps with the mean
-        // weights gives the mean with about half the pilot reads and FMAs of two passes.
-        uint32_t base[2], sh[2], wl[2], wh[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const bool up = pos[2 * s + 1] >= pos[2 * s];
-            base[s] = up ? pos[2 * s] : pos[2 * s + 1];
-            sh[s] = (up ? pos[2 * s + 1] - pos[2 * s] : pos[2 * s] - pos[2 * s + 1]) / (PS * step);
-            wl[s] = up ? wo[2 * s] : wo[2 * s + 1];
-            wh[s] = up ? wo[2 * s + 1] : wo[2 * s];
-        }
-        const uint32_t ntap = nI + max(sh[0], sh[1]);
-        const uint32_t psh = (AI ? 1u : 0u) + (mode ? 0u : 1u);  // log2(PS * step): a shift, not v_mul_lo
-        float2 g[NRX][2];
-#pragma unroll
-        for (int a = 0; a < NRX; ++a) g[a][0] = g[a][1] = make_float2(0.f, 0.f);
-        // taps in chunks of CH, per stream every LDS read of a chunk (weights at clamped indices,
-        // pilots) issued before its FMAs: one LDS latency per chunk and stream instead of per tap,
-        // no exec-mask branches. Taps past a stream's union window carry weight 0 (their read stays
-        // in the row + ZFI_PAD) and add exact zeros, so the per-(antenna, stream) sums are the
-        // tap-ordered sums of the one-tap loop, bit for bit.
-        constexpr uint32_t CH = DNRP_CELLS_CH;
-        for (uint32_t i0 = 0; i0 < ntap; i0 += CH) {
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                __builtin_amdgcn_sched_barrier(0);  // one stream's chunk live at a time
-                float wv[CH];
-                float2 z[CH][NRX];
-#pragma unroll
-                for (uint32_t j = 0; j < CH; ++j) {
-                    const uint32_t i = i0 + j, ih = i - sh[s];  // ih wraps for i < sh
-                    const float lo = wtab[wl[s] + min(i, nI - 1)], hi = wtab[wh[s] + min(ih, nI - 1)];
-                    wv[j] = 0.5f * ((i < nI ? lo : 0.f) + (ih < nI ? hi : 0.f));
-                    const uint32_t p = base[s] + (min(i, nI + sh[s]) << psh);
-                    if constexpr (AI) {
-                        typedef float f4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-                        for (int q = 0; q < NRX / 2; ++q) {
-                            const f4 v = *reinterpret_cast<const f4*>(zfi + p + q * zst * 2);
-                            z[j][2 * q] = make_float2(v.x, v.y);
-                            z[j][2 * q + 1] = make_float2(v.z, v.w);
-                        }
-                    } else {
-#pragma unroll
-                        for (int a = 0; a < NRX; ++a) z[j][a] = zfi[a * NT * zst + p];
-                    }
-                }
-#pragma unroll
-                for (uint32_t j = 0; j < CH; ++j)
-#pragma unroll
-                    for (int a = 0; a < NRX; ++a) {
-                        g[a][s].x = fmaf(z[j][a].x, wv[j], g[a][s].x);
-                        g[a][s].y = fmaf(z[j][a].y, wv[j], g[a][s].y);
-                    }
-            }
-        }
-        float2 n0 = make_float2(0.f, 0.f), n1 = make_float2(0.f, 0.f);
-        float den = 0.f;
-#pragma unroll
-        for (int a = 0; a < NRX; ++a) {  // SFBC pair combining (rx_synced.cpp:1373-1391)
-            const float2 h0 = g[a][0], h1 = g[a][1];
-            n0 = cadd(n0, cadd(cmul(cconj(h0), b.r0[a]), cmul(h1, cconj(b.r1[a]))));
-            n1 = cadd(n1, cadd(cmul(make_float2(-h1.x, -h1.y), cconj(b.r0[a])), cmul(cconj(h0), b.r1[a])));
-            den += cnorm(h0) + cnorm(h1);
-        }
-        emit_cell(cscale(n0, 1.0f / den), b.jj, b.jj, N_bps, bits, llr);
-        emit_cell(cscale(n1, 1.0f / den), b.jj + 1, b.jj, N_bps, bits, llr);
-    }
+    float2 g0[NRX], g1[NRX];
+    eq_interp_first<NRX, NT>(sg, zfi, wtab, zst, b, g0, g1);
+    eq_emit<NRX, NT, NBPS>(A, b, g0, g1, llr);
 }
 
 // ===================================================================== spatial multiplexing (MMSE)
