@@ -1,10 +1,13 @@
-// Internal state of the C-ABI context shared by the host translation units (ctx.cpp: TX / RX
-// phases, sync.cpp: synchronisation). Not part of the public interface.
+// Internal state of the C-ABI context shared by the host translation units (ctx.cpp: context and
+// small tables, tables.cpp: per-configuration device tables, tx.cpp / rx.cpp: the TX and RX phase
+// launches, sync.cpp: synchronisation). Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -184,6 +187,74 @@ struct netid_seq {
     dbuf t1, t2;
 };
 
+// Run-time switches (environment variables): A/B and test hooks. Each is read at one fixed time, by the
+// read_* function of that time below and nowhere else; tests flip the per-call ones on a live context.
+struct switches {
+    // ---- at context creation (read_create)
+    bool timing = false;  // DNRP_TIMING=1 (first character '1'): HIP events around every launch
+    bool eq_twin = true;  // DNRP_EQ_TWIN=0: no twin segments in the epoch receiver's plan (geo::build_rx_plan)
+    // ---- once per PCC call, so that its PDC call agrees (read_pcc)
+    bool rx_snr_front = true;  // DNRP_RX_SNR_FRONT=0: rx_snr gathers the DRS cells from Y (no front-end sums, no pilots)
+    // DNRP_RX_FUSED=1 (and rx_snr_front): the PDC phase through the fused receiver (rx_fused.hip) instead
+    // of Y and rx_cells: parity-tested, slower on MI355X (docs/DESIGN_LOG.md §6)
+    bool rx_fused = false;
+    // DNRP_RX_EPOCH: the PDC phase through the epoch receiver (rx_epoch.hip) -- 1 (default) with 4 or more RX
+    // antennas, where it measured faster (C4: 1.2 ms per 16384-slot chunk; SISO C3 loses, 7.2 vs 5.5 ms per
+    // 8192: one symbol task per wave and epoch), 2 for every geometry it supports, 0 never (Y + rx_cells)
+    uint32_t rx_epoch = 1;
+    uint32_t rx_group = 0;  // DNRP_RX_GROUP=G: the Y path in groups of G packets on two streams (0: one launch set)
+    // ---- per TX call (read_tx)
+    uint64_t tx_big_cap = uint64_t(4) << 30;  // DNRP_TX_BIG_CAP (bytes) lowers it: a test can force several passes
+    // DNRP_TX_MFMA=1 / 2 (f32): polyphase blocks on the matrix cores (polyphase.hpp mf_blocks), opt-in A/B;
+    // the VALU blocks measured faster (docs/DESIGN_LOG.md)
+    uint32_t tx_mfma = 0;
+    // ---- per sync call (read_sync)
+    // DNRP_SYNC_ROUNDS: split detection / coarse-peak rounds ahead of the inline detection. -1 (unset): 2
+    // with several antennas (their peak searches in parallel instead of in series: C4 4 antennas 199k -> 205k
+    // slot-pairs/s), 0 with one (the extra dependent launches lengthen the chain the host waits on: C3 654k
+    // inline vs 573k split, C2 equal; same-box A/B on MI355X)
+    int sync_rounds = -1;
+    // DNRP_SYNC_STREAM=0: the wave step-sum kernel; DNRP_SYNC_PIPE=0: the streaming one with the single-chunk
+    // prefetch; default the pipelined one (one wave per workgroup, a retired segment frees its LDS at once:
+    // sync_steps 4.32 -> 3.81 ms, 176.4k -> 186.0k slot-pairs/s against four waves)
+    dev::sync_steps_kind sync_steps = dev::SYNC_STEPS_PIPE;
+    // DNRP_SYNC_TRANCHE: 0 = one tranche; "32,64" = explicit tranche sizes in steps (geo::sync_tranches' forced)
+    bool sync_tranche_set = false;
+    std::vector<uint64_t> sync_tranche;
+};
+
+inline void read_create(switches& s) {
+    const char *tm = std::getenv("DNRP_TIMING"), *tw = std::getenv("DNRP_EQ_TWIN");
+    s.timing = tm && tm[0] == '1';
+    s.eq_twin = !tw || std::atoi(tw) != 0;
+}
+inline void read_pcc(switches& s) {
+    const char *e = std::getenv("DNRP_RX_SNR_FRONT"), *f = std::getenv("DNRP_RX_FUSED");
+    const char *ep = std::getenv("DNRP_RX_EPOCH"), *gr = std::getenv("DNRP_RX_GROUP");
+    s.rx_snr_front = !e || std::atoi(e);
+    s.rx_fused = s.rx_snr_front && f && std::atoi(f);
+    s.rx_epoch = ep ? static_cast<uint32_t>(std::atoi(ep)) : 1u;
+    s.rx_group = gr ? static_cast<uint32_t>(std::atoi(gr)) : 0u;
+}
+inline void read_tx(switches& s) {
+    const char *e = std::getenv("DNRP_TX_BIG_CAP"), *mf = std::getenv("DNRP_TX_MFMA");
+    s.tx_big_cap = std::min<uint64_t>(uint64_t(4) << 30, e ? std::strtoull(e, nullptr, 10) : ~uint64_t(0));
+    s.tx_mfma = mf ? static_cast<uint32_t>(std::min(2, std::max(0, std::atoi(mf)))) : 0u;
+}
+inline void read_sync(switches& s) {
+    const char *rd = std::getenv("DNRP_SYNC_ROUNDS"), *ss = std::getenv("DNRP_SYNC_STREAM");
+    const char *pp = std::getenv("DNRP_SYNC_PIPE"), *tr = std::getenv("DNRP_SYNC_TRANCHE");
+    s.sync_rounds = rd ? std::max(0, std::atoi(rd)) : -1;
+    s.sync_steps = ss && !std::atoi(ss) ? dev::SYNC_STEPS_WAVE : pp && !std::atoi(pp) ? dev::SYNC_STEPS_STREAM : dev::SYNC_STEPS_PIPE;
+    s.sync_tranche_set = tr != nullptr;
+    s.sync_tranche.clear();
+    for (char* q = nullptr; tr && *tr; tr = q + 1) {
+        const unsigned long v = std::strtoul(tr, &q, 10);
+        if (q == tr) break;
+        s.sync_tranche.push_back(v);
+        if (*q != ',') break;
+    }
+}
 
 struct sync_tables {  // per (u, b) of the searched STF: sync_chunk_t / crosscorrelator_t constructors
     uint32_t u = 0, b = 0, n_pattern = 0, stf_len = 0, pattern = 0, step = 0, D = 0, bos = 0;
@@ -193,6 +264,17 @@ struct sync_tables {  // per (u, b) of the searched STF: sync_chunk_t / crosscor
     uint32_t m_star = 0, p_star = 0, npp = 0;
     dbuf taps, taps_pp, tmpl_f, tw_fft;
 };
+
+// tables.cpp: the tables of a configuration, built and uploaded at its first use (nullptr: *err set)
+tx_tables* get_tx(dnrp_ctx* ctx, const dnrp_psdef& d, int* err);
+rx1_tables* get_rx1(dnrp_ctx* ctx, uint32_t u, uint32_t b, uint32_t N_eff_TX, int* err);
+rx2_tables* get_rx2(dnrp_ctx* ctx, const dnrp_psdef& d, int* err);
+// ctx.cpp: the PDC scrambling sequences of a network ID, at least nbits long
+int ensure_seq(dnrp_ctx* ctx, netid_seq& s, uint32_t nid, uint32_t nbits);
+// rx.cpp: front-end arguments of a PCC-phase geometry; plan: the phase plan whose DRS SNR sums (and
+// pilots) the front end computes, where it does
+dev::rx_front_args front_args(dnrp_ctx* ctx, rx1_tables* t, const float* iq, const uint32_t* sel,
+                              const rx_plan_dev* plan = nullptr);
 
 }  // namespace dnrp::host
 
@@ -219,18 +301,8 @@ struct dnrp_ctx {
     dbuf zd;
     uint32_t zd_dops = 0, zd_row = 0;
     std::tuple<void*, size_t, uint32_t, uint32_t, uint32_t> zd_key{};
-    // per PCC call: the DRS SNR sums (and pilots) come from the front end (DNRP_RX_SNR_FRONT, read
-    // once per PCC call so that its PDC call agrees), and the PDC phase may take the fused receiver
-    bool rx_snr_front = true, rx_fused = true;
-    // PDC phase in packet groups (DNRP_RX_GROUP packets, 0: one launch set): the front end of group g+1
-    // on the caller's stream beside the back end of group g on rx_aux, Y of a group re-read from the
-    // caches; fork / join through rx_fork / rx_join
-    uint32_t rx_group = 0;
-    // PDC phase through the epoch receiver (kernels/rx_epoch.hip, DNRP_RX_EPOCH): 0 off, 1 where it
-    // applies and pays (N_RX >= 4), 2 wherever it applies (tests)
-    uint32_t rx_epoch = 1;
-    // twin segments in the epoch receiver's plan (geo::build_rx_plan; DNRP_EQ_TWIN=0 at context creation: off)
-    bool eq_twin = true;
+    dnrp::host::switches sw;  // each section as of its read time
+    // PDC phase in packet groups (sw.rx_group): the back ends' stream, fork / join through rx_fork / rx_join
     hipStream_t rx_aux = nullptr;
     hipEvent_t rx_fork = nullptr, rx_join = nullptr;
     uint32_t rx_mode = 0;  // DNRP_RX_MODE_* (dnrp_ctx_set_rx_mode)
@@ -253,8 +325,7 @@ struct dnrp_ctx {
     // simulated channel (channel.cpp): per-call link realisations
     dbuf chan_tab;
     pinned st_chan;
-    // timing: HIP events recorded on the caller's stream around every launch (DNRP_TIMING=1)
-    bool timing = false;
+    // timing: HIP events recorded on the caller's stream around every launch (sw.timing)
     struct ev_pool {
         std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
         size_t used = 0;
@@ -276,7 +347,7 @@ struct dnrp_ctx {
             }
     }
     void tic(const char* name, hipStream_t s) {
-        if (!timing) return;
+        if (!sw.timing) return;
         auto& pool = ev[name];
         if (pool.used == pool.ev.size()) {
             std::pair<hipEvent_t, hipEvent_t> p{};
@@ -287,7 +358,7 @@ struct dnrp_ctx {
         (void)hipEventRecord(pool.ev[pool.used].first, s);
     }
     void toc(const char* name, hipStream_t s) {
-        if (!timing) return;
+        if (!sw.timing) return;
         auto& pool = ev[name];
         (void)hipEventRecord(pool.ev[pool.used].second, s);
         ++pool.used;

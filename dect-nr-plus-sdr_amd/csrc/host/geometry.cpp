@@ -855,4 +855,121 @@ rx_plan_t build_rx_plan(const maps_t& m, const std::vector<op_t>& ops, uint32_t 
     return p;
 }
 
+namespace {
+bool is_drs(const maps_t& m, uint32_t l) {
+    for (const auto& d : m.drs)
+        if (d.l == l) return true;
+    return false;
+}
+const drs_sym_t* latest_drs(const maps_t& m, uint32_t ts) {  // the latest DRS symbol carrying stream ts
+    const drs_sym_t* last = nullptr;
+    for (const auto& d : m.drs)
+        if (d.ts_first <= ts && ts <= d.ts_last) last = &d;
+    return last;
+}
+// the phase's DRS symbols: after the PCC phase's last symbol pm
+std::vector<uint16_t> phase_drs(const maps_t& m, uint32_t pm) {
+    std::vector<uint16_t> v;
+    for (const auto& d : m.drs)
+        if (d.l > pm && d.l <= m.N_DF) v.push_back(static_cast<uint16_t>(d.l));
+    return v;
+}
+}  // namespace
+
+rx_mimo_cells_t rx_mimo_cells(const maps_t& m, const rx_plan_t& plan, uint32_t N_TS) {
+    constexpr uint32_t NW = prm::RX_MIMO_WIDEBAND_CELLS;
+    const uint32_t nd = static_cast<uint32_t>(m.drs_v.size() / 8), step = nd / NW, off = step / 2;
+    rx_mimo_cells_t r{std::vector<uint32_t>(N_TS * NW, 0), std::vector<float>(N_TS * NW, 1.f),
+                      std::vector<uint32_t>(N_TS * NW, 0)};
+    for (uint32_t ts = 0; ts < N_TS; ++ts) {
+        const drs_sym_t* last = latest_drs(m, ts);
+        uint32_t dop = 0;  // DRS op of the phase plan at that symbol
+        while (last && dop < plan.dl.size() && plan.dl[dop] != last->l) ++dop;
+        for (uint32_t c = 0; c < NW; ++c) {
+            const uint32_t i = off + c * step;
+            r.zcells[ts * NW + c] = (dop << 16) | i;
+            if (!last) continue;
+            r.cells[ts * NW + c] = (last->l << 16) | m.drs_k[(last->parity * 4 + ts % 4) * nd + i];
+            r.signs[ts * NW + c] = m.drs_v[ts * nd + i];
+        }
+    }
+    return r;
+}
+
+rx_fused_syms_t rx_fused_syms(const maps_t& m, const rx_plan_t& plan, uint32_t N_eff_TX, uint32_t pm) {
+    rx_fused_syms_t r;
+    const bool pairs = N_eff_TX > 1;
+    bool ok = N_eff_TX == 1 || N_eff_TX == 2 || N_eff_TX == 4;
+    for (const auto& e : plan.epochs)
+        for (uint32_t s = e.seg0; s < e.seg1 && ok; ++s) {
+            const auto& g = plan.segs[s];
+            ok = g.kind == OP_PDC && g.drs_cnt > 0;
+            uint32_t j = g.j0;
+            for (uint32_t l = 0; l <= m.N_DF && j < g.j1 && ok; ++l) {
+                const uint32_t c0 = m.pdc_sym_off[l], c1 = m.pdc_sym_off[l + 1];
+                if (c1 <= j || c0 == c1) continue;
+                if (c0 != j || c1 > g.j1 || (pairs && ((c0 | c1) & 1u))) {
+                    ok = false;
+                    break;
+                }
+                rx_fsym_t f{};
+                f.l = l;
+                f.j0 = c0;
+                f.j1 = c1;
+                const bool from_y = l <= pm || is_drs(m, l);
+                // every occupied subcarrier but DC in order: the kernel computes the subcarriers
+                const uint32_t N = 56 * m.b;
+                bool full = c1 - c0 == N;
+                for (uint32_t c = 0; c < N && full; ++c) full = m.pdc_k[c0 + c] == c + (c >= N / 2 ? 1u : 0u);
+                f.info = (g.mode & 1u) | (g.swap & 3u) << 1 | (g.off & 0xFFu) << 4 | (from_y ? 1u : 0u) << 12 |
+                         (full ? 1u : 0u) << 13;
+                f.rel = g.rel;
+                f.drs_cnt = g.drs_cnt;
+                std::memcpy(f.src, e.src, sizeof(f.src));
+                r.fsym.push_back(f);
+                j = c1;
+            }
+            ok = ok && j == g.j1;
+        }
+    r.drs_syms = phase_drs(m, pm);
+    for (const uint16_t l : r.drs_syms) r.drs_y = r.drs_y || m.pdc_sym_off[l + 1] > m.pdc_sym_off[l];
+    r.ok = ok && !r.fsym.empty();
+    return r;
+}
+
+rx_epoch_syms_t rx_epoch_syms(const maps_t& m, const rx_plan_t& plan, uint32_t pm) {
+    rx_epoch_syms_t r;
+    r.ok = !plan.epochs.empty();
+    r.off.push_back(0);
+    std::vector<int> owner(m.N_DF + 2, -1);
+    for (size_t e = 0; e < plan.epochs.size(); ++e) {
+        std::vector<uint32_t> ls;
+        for (uint32_t s = plan.epochs[e].seg0; s < plan.epochs[e].seg1; ++s) {
+            const auto& g = plan.segs[s];
+            if (g.kind != OP_PDC) {
+                r.ok = false;
+                continue;
+            }
+            for (uint32_t l = 1; l <= m.N_DF; ++l)
+                if (m.pdc_sym_off[l] < g.j1 && m.pdc_sym_off[l + 1] > g.j0 && l > pm && !is_drs(m, l)) ls.push_back(l);
+        }
+        std::sort(ls.begin(), ls.end());
+        ls.erase(std::unique(ls.begin(), ls.end()), ls.end());
+        for (uint32_t l : ls) {
+            if (owner[l] >= 0) r.ok = false;
+            owner[l] = static_cast<int>(e);
+            r.sym.push_back(static_cast<uint16_t>(l));
+        }
+        r.off.push_back(static_cast<uint16_t>(r.sym.size()));
+    }
+    r.drs = phase_drs(m, pm);
+    return r;
+}
+
+bool rx_twin_plan_ok(const maps_t& m, const rx_plan_t& plain, const rx_plan_t& twin) {
+    bool any = false;
+    for (const auto& g : twin.segs) any = any || g.twin;
+    return any && twin.epochs.size() == plain.epochs.size() && m.Nf <= 1024 && m.N_DF + 1 < (1u << 12);
+}
+
 }  // namespace dnrp::geo

@@ -84,6 +84,16 @@ struct resampler_t {
     std::vector<float> h;
 };
 resampler_t make_resampler(uint32_t L, uint32_t M, uint32_t os_min, uint32_t user);  // user: prm::rs_user
+// alignment of the polyphase blocks: the first output m_star whose filter phase is 0, and the input
+// sample p_star it is centred on (delay + m_star M = p_star L)
+struct rs_align_t {
+    uint32_t m_star, p_star;
+};
+inline rs_align_t resampler_align(const resampler_t& rs) {
+    uint32_t m = 0;
+    while ((rs.delay + m * rs.M) % rs.L) ++m;
+    return {m, (rs.delay + m * rs.M) / rs.L};
+}
 
 // Wiener LUT for one (N_step_virtual, b, SNR profile) — channel_lut.cpp:168-620
 struct lut_t {
@@ -141,7 +151,46 @@ struct rx_plan_t {
 rx_plan_t build_rx_plan(const maps_t& m, const std::vector<op_t>& ops, uint32_t N_eff_TX, bool pair_units = true,
                         bool twin = false);
 
-// dnrp_rx_sync_batch's tranche schedule (host/sync.cpp): the step frontiers of one call, the last n_steps
-std::vector<uint32_t> sync_tranches(uint32_t n_steps, uint32_t step, uint32_t stf_len, uint32_t n, uint32_t n_ant);
+// Tables of one PDC phase derived from its maps and plain plan (get_rx2 uploads them; pm: the PCC
+// phase's last symbol, build_rx_ops' pcc_max_symbol).
+// MIMO report (estimator_mimo.cpp:80-160): per transmit stream the latest DRS symbol carrying it and its
+// wideband cells at DRS cell step / 2 + c step (step = N_DRS_cells_b / 4), c = 0..3
+struct rx_mimo_cells_t {
+    std::vector<uint32_t> cells;   // [N_TS][4] symbol << 16 | subcarrier index
+    std::vector<float> signs;      // [N_TS][4] DRS value (+-1)
+    std::vector<uint32_t> zcells;  // [N_TS][4] the same cells in the zero-forced pilots: plan DRS op << 16 | DRS cell
+};
+rx_mimo_cells_t rx_mimo_cells(const maps_t& m, const rx_plan_t& plan, uint32_t N_TS);
+// Fused PDC receiver (kernels/rx_fused.hip): one entry per PDC-bearing symbol with the event of its plan
+// segment and the pilot sources of its epoch (layout of dev::rx_fsym). ok where every segment is a run of
+// whole symbols and, for transmit diversity, every symbol has an even cell count. drs_syms: the phase's DRS
+// symbols, which the front end runs first; drs_y: some of them carry PDC cells (their bins then go to Y)
+struct rx_fsym_t {
+    uint32_t l, j0, j1, info, rel, drs_cnt;  // info: mode | swap << 1 | off << 4 | from_y << 12 | full << 13
+    uint16_t src[4][2];
+};
+struct rx_fused_syms_t {
+    bool ok = false, drs_y = false;
+    std::vector<rx_fsym_t> fsym;
+    std::vector<uint16_t> drs_syms;
+};
+rx_fused_syms_t rx_fused_syms(const maps_t& m, const rx_plan_t& plan, uint32_t N_eff_TX, uint32_t pm);
+// Epoch receiver (kernels/rx_epoch.hip): per plan epoch e the symbols sym[off[e] .. off[e + 1]) whose bins
+// its cells read, minus the PCC phase's (in Y from the PCC call) and the DRS symbols (drs: the DRS pass
+// ahead of it). ok where every segment is a PDC segment and no symbol is claimed by two epochs
+struct rx_epoch_syms_t {
+    bool ok = false;
+    std::vector<uint16_t> off, sym, drs;
+};
+rx_epoch_syms_t rx_epoch_syms(const maps_t& m, const rx_plan_t& plan, uint32_t pm);
+// the epoch receiver takes the twin plan where it has a twin segment, keeps the plain plan's epochs and
+// fits rx_epoch_kernel's packing of a twin unit: subcarriers 10 bits each, symbol 12 bits
+bool rx_twin_plan_ok(const maps_t& m, const rx_plan_t& plain, const rx_plan_t& twin);
+
+// dnrp_rx_sync_batch's tranche schedule (host/sync.cpp): the step frontiers of one call, the last n_steps.
+// forced: explicit tranche sizes in steps instead of the rule (the DNRP_SYNC_TRANCHE switch), the last
+// tranche taking the rest
+std::vector<uint32_t> sync_tranches(uint32_t n_steps, uint32_t step, uint32_t stf_len, uint32_t n, uint32_t n_ant,
+                                    const std::vector<uint64_t>* forced = nullptr);
 
 }  // namespace dnrp::geo

@@ -9,9 +9,7 @@
 #include <vector>
 
 #include "../params.hpp"
-#include "dnrp.h"
-#include "geometry.hpp"
-#include "kernels.hpp"
+#include "ctx_internal.hpp"
 
 namespace {
 
@@ -183,7 +181,7 @@ int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, floa
             if (n_arg != 2) return DNRP_EINVAL;
             v.push_back(static_cast<float>(geo::W_codebooks(a(0), a(1))));
         } else if (n == "cells_lds_bytes") {  // (u_max, b_max, b, N_RX, N_eff_TX): rx_cells_kernel's LDS
-            // staging for the geometry (ctx.cpp launch_back: above 160 KiB -> DNRP_EUNSUPPORTED); the
+            // staging for the geometry (rx.cpp launch_back: above 160 KiB -> DNRP_EUNSUPPORTED); the
             // weight-table slots as get_rx1 sizes them from the Wiener LUTs of both modes
             if (n_arg != 5 || a(2) == 0 || a(2) > a(1) || a(4) == 0 || a(4) > 8) return DNRP_EINVAL;
             const uint32_t Nsv = a(4) <= 2 ? 5 : 10;
@@ -219,7 +217,10 @@ int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, floa
             // frontiers for that geometry (the last one n_steps); honours DNRP_SYNC_TRANCHE as the call does
             if (n_arg != 5 || a(0) == 0 || a(1) == 0 || a(2) == 0 || a(3) == 0 || a(4) == 0 || a(0) > (1u << 24))
                 return DNRP_EINVAL;
-            for (const uint32_t f : geo::sync_tranches(a(0), a(1), a(2), a(3), a(4))) v.push_back(static_cast<float>(f));
+            host::switches sw;
+            host::read_sync(sw);
+            for (const uint32_t f : geo::sync_tranches(a(0), a(1), a(2), a(3), a(4), sw.sync_tranche_set ? &sw.sync_tranche : nullptr))
+                v.push_back(static_cast<float>(f));
         } else if (n == "stf_cover_sequence") {
             v.assign(prm::STF_COVER, prm::STF_COVER + 9);
         } else if (n == "symbol_cells") {  // (b, N_TS, N_eff_TX, N_DF): per symbol l = 0..N_DF: PCC, PDC, DRS cells
@@ -270,6 +271,25 @@ int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, floa
                         v.push_back(static_cast<float>(x));
                 }
             }
+        } else if (n == "rx_epoch_syms") {
+            // (b, N_TS, N_eff_TX, N_DF, mode_lr, stride): the epoch receiver's symbol ownership for that PDC
+            // phase (geo::rx_epoch_syms, as get_rx2 takes it): ok, then per plan epoch its symbol count and
+            // symbols, then the DRS-pass symbols
+            if (n_arg != 6 || a(0) == 0 || a(0) > 16 || a(1) == 0 || a(1) > 8 || a(2) == 0 || a(2) > 8 || a(3) == 0 ||
+                a(3) > 1024 || a(5) == 0)
+                return DNRP_EINVAL;
+            const auto m = geo::build_maps(a(0), a(1), a(2), a(3));
+            std::vector<geo::op_t> pcc_ops, pdc_ops;
+            uint32_t pm = 0;
+            geo::build_rx_ops(m, a(2), a(3), a(4) != 0, a(5), pcc_ops, pdc_ops, pm);
+            const auto p = geo::build_rx_plan(m, pdc_ops, a(2));
+            const auto ep = geo::rx_epoch_syms(m, p, pm);
+            v.push_back(ep.ok && p.dl.size() <= dev::RX_MAX_DOPS ? 1.f : 0.f);
+            for (size_t e = 0; e + 1 < ep.off.size(); ++e) {
+                v.push_back(static_cast<float>(ep.off[e + 1] - ep.off[e]));
+                for (uint32_t i = ep.off[e]; i < ep.off[e + 1]; ++i) v.push_back(static_cast<float>(ep.sym[i]));
+            }
+            for (const uint16_t l : ep.drs) v.push_back(static_cast<float>(l));
         } else {
             return DNRP_EINVAL;
         }

@@ -127,8 +127,9 @@ sync_tables* get_sync(dnrp_ctx* ctx, uint32_t u, uint32_t b, int* err) {
     // sync resampler: RX direction, L and M swapped (sync_chunk.cpp:40-48)
     t->rs = geo::make_resampler(c.M, c.L, c.os_min, prm::RS_SYNC);
     if (!(c.L == 1 && c.M == 1)) {
-        while ((t->rs.delay + t->m_star * t->rs.M) % t->rs.L) ++t->m_star;
-        t->p_star = (t->rs.delay + t->m_star * t->rs.M) / t->rs.L;
+        const auto al = geo::resampler_align(t->rs);
+        t->m_star = al.m_star;
+        t->p_star = al.p_star;
     }
     const auto rs_tx = geo::make_resampler(c.L, c.M, c.os_min, prm::RS_TX);  // stf_template.cpp: TX filter
     std::vector<float2> tf(size_t(t->n_templates) * nf);
@@ -165,21 +166,15 @@ sync_tables* get_sync(dnrp_ctx* ctx, uint32_t u, uint32_t b, int* err) {
 //    or the call's step sums are under 2^28 DECT samples (~0.6 ms of sync_steps on MI355X): there
 //    the added launches per tranche (step sums, split rounds, inline detection) are not paid back
 //    (C2: 4-sample steps, launch-latency bound).
-// DNRP_SYNC_TRANCHE (read per call: tests and A/B runs switch it): 0 = one tranche; a comma list
-// "32,64" = explicit tranche sizes in steps, the last tranche taking the rest.
+// forced (switches::sync_tranche, DNRP_SYNC_TRANCHE): explicit tranche sizes instead.
 // (dnrp_query_table "sync_tranches" reports it.)
-std::vector<uint32_t> dnrp::geo::sync_tranches(uint32_t n_steps, uint32_t step, uint32_t stf_len, uint32_t n, uint32_t n_ant) {
+std::vector<uint32_t> dnrp::geo::sync_tranches(uint32_t n_steps, uint32_t step, uint32_t stf_len, uint32_t n, uint32_t n_ant,
+                                               const std::vector<uint64_t>* forced) {
     std::vector<uint32_t> fr;
-    if (const char* e = std::getenv("DNRP_SYNC_TRANCHE")) {
+    if (forced) {
         uint32_t at = 0;
-        for (const char* p = e; *p;) {
-            char* q = nullptr;
-            const unsigned long v = std::strtoul(p, &q, 10);
-            if (q == p) break;
+        for (const uint64_t v : *forced)
             if (v > 0 && v < n_steps - at) fr.push_back(at += static_cast<uint32_t>(v));
-            p = *q == ',' ? q + 1 : q;
-            if (*q != ',') break;
-        }
         fr.push_back(n_steps);
         return fr;
     }
@@ -279,21 +274,19 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
     a.prof = do_prof ? prof.as<unsigned long long>() : nullptr;
     if (do_prof) HIPCHK(hipMemsetAsync(prof.p, 0, size_t(n) * 32 * 8, st));
 #endif
+    switches& sw = ctx->sw;
+    read_sync(sw);  // per call: tests switch them at run time
     // detection + coarse peak: `rounds` split rounds (detection-only workgroups, then one coarse-peak
     // workgroup per (window, antenna) of every pending detection), then the inline form finishes what
-    // is left (windows with more detections than rounds); DNRP_SYNC_ROUNDS=0: the inline form alone.
-    // Default: split with several antennas (their peak searches run in parallel instead of in series:
-    // C4 4 antennas 199k -> 205k slot-pairs/s), inline with one (no series to break up, and the extra
-    // dependent launches lengthen the sync chain the host waits on: C3 654k inline vs 573k split,
-    // C2 equal; same-box A/B on MI355X). Read per call (tests switch it at run time).
-    const char* rd_e = std::getenv("DNRP_SYNC_ROUNDS");
-    const int rounds = !dev::sync_peak_ok(a) ? 0 : rd_e ? std::max(0, std::atoi(rd_e)) : (a.n_ant > 1 ? 2 : 0);
+    // is left (windows with more detections than rounds); default sw.sync_rounds
+    const int rounds = !dev::sync_peak_ok(a) ? 0 : sw.sync_rounds >= 0 ? sw.sync_rounds : (a.n_ant > 1 ? 2 : 0);
     // Step sums in tranches (sync_tranches above): per tranche the step-sum launch over its steps,
     // then the detection launches up to that frontier. A window that reaches max_reports is finished
     // (pend = 2) and the later tranches' step-sum waves of it leave at once; a window whose scan
     // reaches the frontier saves its loop registers and goes on in the next tranche. Stream-ordered
     // throughout; the timer names accumulate over the tranches.
-    const std::vector<uint32_t> frontier = geo::sync_tranches(a.n_steps, a.step, a.stf_len, n, a.n_ant);
+    const std::vector<uint32_t> frontier =
+        geo::sync_tranches(a.n_steps, a.step, a.stf_len, n, a.n_ant, sw.sync_tranche_set ? &sw.sync_tranche : nullptr);
     a.first = 1;
     a.rounds = static_cast<uint32_t>(rounds);  // the first `rounds` detections of a window go to sync_peak, in any tranche
     for (size_t k = 0; k < frontier.size(); ++k) {
@@ -301,7 +294,7 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
         a.s_hi = frontier[k];
         a.skip = k ? 1u : 0u;  // the first tranche must not read the state: not initialised yet
         ctx->tic("sync_steps", st);
-        if (dev::launch_sync_steps(a, n, st) != hipSuccess) return DNRP_EDEVICE;
+        if (dev::launch_sync_steps(a, n, st, sw.sync_steps) != hipSuccess) return DNRP_EDEVICE;
         ctx->toc("sync_steps", st);
         for (int r = 0; r < rounds; ++r) {
             ctx->tic("sync_detect", st);

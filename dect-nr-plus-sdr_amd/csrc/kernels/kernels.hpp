@@ -1,4 +1,4 @@
-// Kernel argument blocks and launchers shared by the host context (host/ctx.cpp) and the HIP
+// Kernel argument blocks and launchers shared by the host context (host/tx.cpp, rx.cpp, sync.cpp) and the HIP
 // kernels (kernels/*.hip). Plain structs, passed by value as kernel arguments.
 #pragma once
 
@@ -22,7 +22,7 @@ enum : uint32_t {
     CODE_STF = 4u << 29,
     CODE_MASK = 7u << 29,
     // one-hot W rows (tx.hip TXS_TXDIV1 / TXS_SM1): the code of a bin as seen by the antenna whose
-    // nonzero W entry is stream ts (host-built per ts, ctx.cpp). Type PCC / PDC / DRS only where that
+    // nonzero W entry is stream ts (host-built per ts, tables.cpp). Type PCC / PDC / DRS only where that
     // stream carries the cell (else 0); bits 0..19: the symbol index to map (SFBC partner or spatial
     // stream resolved), OH_FX / OH_FY: sign of its re / im part flipped (DRS: the point (1, 0), OH_FX
     // for the value -1)
@@ -411,7 +411,10 @@ struct sync_state {  // sync_detect_kernel's loop registers (autocorrelator_dete
                     // of a window go to sync_peak_kernel, the later ones to the inline search, however
                     // the tranches cut the search
 };
-hipError_t launch_sync_steps(const sync_args& a, uint32_t n, hipStream_t st);
+// the most specialised step-sum kernel the launch may take, where the geometry allows it (the caller's
+// A/B choice, host/ctx_internal.hpp switches::sync_steps)
+enum sync_steps_kind : uint32_t { SYNC_STEPS_WAVE, SYNC_STEPS_STREAM, SYNC_STEPS_PIPE };
+hipError_t launch_sync_steps(const sync_args& a, uint32_t n, hipStream_t st, sync_steps_kind kind);
 hipError_t launch_sync_detect(const sync_args& a, uint32_t n, hipStream_t st);
 hipError_t launch_sync_detect_split(const sync_args& a, uint32_t n, hipStream_t st);
 hipError_t launch_sync_peak(const sync_args& a, uint32_t n, hipStream_t st);

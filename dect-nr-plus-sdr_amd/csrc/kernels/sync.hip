@@ -1702,15 +1702,12 @@ constexpr int SYNC_WPG = SYNC_WPG_DEF;  // waves per workgroup of the wave kerne
                                 // 12.55 / 12.65, 160 -> 1 x 1440 12.61 / 12.65 (same box)
 #endif
 
-hipError_t launch_sync_steps(const sync_args& a, uint32_t n, hipStream_t st) {
-    // DNRP_SYNC_STREAM=0 selects the wave kernel below (read per call: tests switch it at run time)
-    const char* ss_e = std::getenv("DNRP_SYNC_STREAM");
-    const int ss_env = ss_e ? std::atoi(ss_e) : 1;
+hipError_t launch_sync_steps(const sync_args& a, uint32_t n, hipStream_t st, sync_steps_kind kind) {
     // the tranche [s_lo, s_hi) of the window's steps: only the segments / parts / tiles that cover it
     // are launched (one tranche over all steps: the grids below are the whole-window ones)
     if (a.s_lo >= a.s_hi || a.s_hi > a.n_steps) return hipErrorInvalidValue;
     const uint32_t n_rng = a.s_hi - a.s_lo;
-    if (ss_env && a.L == 9 && a.M == 10 && a.hl == 24 && a.step % 4 == 0 && a.step >= 4 &&
+    if (kind != SYNC_STEPS_WAVE && a.L == 9 && a.M == 10 && a.hl == 24 && a.step % 4 == 0 && a.step >= 4 &&
         64u * 9u + a.step + a.pattern + 9u <= SS_RING) {
         // segments of ~32 chunks per (window, antenna): enough waves to fill the chip, little warm-up
         // segments of at most DNRP_SS_SEG_CHUNKS chunks, balanced: ceil(n_steps / max) segments of
@@ -1722,12 +1719,10 @@ hipError_t launch_sync_steps(const sync_args& a, uint32_t n, hipStream_t st) {
         const uint64_t waves = uint64_t(n) * a.n_ant * n_seg;
         const size_t lds = SS_WPG * size_t(ss_inbuf<9, 10, 24>() + SS_RING) * sizeof(float2);
         const dim3 g(static_cast<uint32_t>((waves + SS_WPG - 1) / SS_WPG)), b(64 * SS_WPG);
-        // one wave per workgroup: a retired segment frees its LDS at once (A/B on MI355X: sync_steps
-        // 4.32 -> 3.81 ms, 176.4k -> 186.0k slot-pairs/s against four); DNRP_SYNC_PIPE=0: the
-        // single-chunk-prefetch form (read per call: tests switch it at run time). Compile-time sync
-        // taps where the run-time taps are the generated ones (neutral, 3.48 ms both; docs/DESIGN_LOG.md §6)
-        const char* pp_e = std::getenv("DNRP_SYNC_PIPE");
-        const bool pipe = !pp_e || std::atoi(pp_e);
+        // the pipelined kernel, one wave per workgroup, unless the caller keeps to the single-chunk-prefetch
+        // form. Compile-time sync taps where the run-time taps are the generated ones (neutral, 3.48 ms
+        // both; docs/DESIGN_LOG.md §6)
+        const bool pipe = kind == SYNC_STEPS_PIPE;
         if (a.step == 64 && pipe && a.pattern % 16 == 0 && 64u * 9u + a.step + a.pattern + 9u <= SS_PRING) {
             const size_t plds = size_t(ss_inbuf<9, 10, 24>() + SS_PRING) * sizeof(float2);
             if (a.ct_taps)

@@ -578,7 +578,7 @@ struct txs_wave {
         v = (ty == CODE_PDC || ty == CODE_DRS || (PCC && ty == CODE_PCC)) ? v : make_float2(0.f, 0.f);
         return v;  // wrow carries scale_df (one multiply per W entry instead of two per bin)
     }
-    // TXS_TXDIV1 / TXS_SM1 from the antenna stream's own code table (ctx.cpp, kernels.hpp OH_*):
+    // TXS_TXDIV1 / TXS_SM1 from the antenna stream's own code table (tables.cpp, kernels.hpp OH_*):
     // the pair tests, the partner index and its flips were resolved on the host, so a bin is one
     // table read, the flips as sign XORs and one complex product -- a DRS cell as the point (+-1, 0)
     // (its sign an OH_FX flip), an empty cell as a zero W entry (bin_df's TXS_TXDIV1 branch, equal

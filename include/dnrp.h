@@ -377,7 +377,10 @@ const char* dnrp_param_name(uint32_t index);
  *   "txdiv_pairs" (N_TS)         Y_i_t::index_N_TS_x rows A0 B0 A1 B1 ... (transmit_diversity_precoding.cpp:48-75)
  *   "stf_cover_sequence" ()      stf_t::cover_sequence (stf.hpp:146-151)
  *   "cells_lds_bytes" (u_max, b_max, b, N_RX, N_eff_TX)   LDS bytes of the PDC equaliser's staging for
- *                                the geometry; above 160 KiB dnrp_rx_*_batch return DNRP_EUNSUPPORTED */
+ *                                the geometry; above 160 KiB dnrp_rx_*_batch return DNRP_EUNSUPPORTED
+ *   "rx_epoch_syms" (b, N_TS, N_eff_TX, N_DF, mode_lr, stride)   the epoch receiver's symbol ownership of
+ *                                the PDC phase: ok (0 / 1), per plan epoch its symbol count and symbols,
+ *                                then the DRS-pass symbols */
 int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, float* out, uint32_t cap);
 
 /* Kernel timing (only when the environment has DNRP_TIMING=1 at dnrp_ctx_create): HIP events

@@ -346,7 +346,7 @@ def test_rx_largest_cells_geometry(monkeypatch):
 def test_rx_fused_growing_batch(monkeypatch):
     """DNRP_RX_FUSED=1 with a small PCC/PDC batch and then a larger one in the same context: the pilot
     buffer zd is reallocated (possibly at the same address) and its op-less interlace slot must be
-    zeroed again (ctx.cpp zd_key includes the size) -- both batches at parity."""
+    zeroed again (rx.cpp zd_key includes the size) -- both batches at parity."""
     import dnrp
     monkeypatch.setenv("DNRP_RX_FUSED", "1")
     rng = np.random.default_rng(23)
@@ -791,7 +791,7 @@ def test_rx_llr_clamp(monkeypatch):
     assert abs(rep1[0].snr_dB - r["snr_pcc"]) < 0.05 and abs(rep2[0].snr_dB - r["snr_pdc"]) < 0.05
 
 
-# ---- DNRP_RX_GROUP: the Y path in packet groups on two streams (ctx.cpp: fork / join events)
+# ---- DNRP_RX_GROUP: the Y path in packet groups on two streams (rx.cpp pdc_grouped_y: fork / join events)
 def test_rx_group_tail_and_mixed_profiles(monkeypatch):
     """5 packets in groups of 2, 2 and 1 (a tail group), the lut_cases C4 batch with every profile and both
     step packets: each group's back end reads its own packets' picks and Y."""
