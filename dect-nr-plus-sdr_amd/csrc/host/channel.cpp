@@ -10,7 +10,7 @@
 #include <random>
 #include <vector>
 
-#include "ctx_internal.hpp"
+#include "channel_internal.hpp"
 
 using namespace dnrp;
 using namespace dnrp::host;
@@ -19,7 +19,7 @@ namespace {
 
 // generic power delay profiles (link.hpp:88-108 = 3GPP TS 36.104 Annex B EPA / EVA / ETU, via
 // srsRAN fading.c): delays in ns, powers in dB; NAN ends a profile
-constexpr uint32_t PDP_N = 3, PDP_TAPS = 9, N_SIN = 40;  // WIRELESS_CHANNEL_DOUBLY_NOF_{PROFILE,TAPS,SINUSOIDS}
+constexpr uint32_t PDP_N = 3, PDP_TAPS = 9, N_SIN = CH_N_SIN;  // WIRELESS_CHANNEL_DOUBLY_NOF_{PROFILE,TAPS,SINUSOIDS}
 constexpr double PDP_DELAY_NS[PDP_N][PDP_TAPS] = {{0, 30, 70, 90, 110, 190, 410, NAN, NAN},
                                                   {0, 30, 150, 310, 370, 710, 1090, 1730, 2510},
                                                   {0, 50, 120, 200, 230, 500, 1600, 2300, 5000}};
@@ -39,6 +39,10 @@ double tau_rms_ns(const double* d, const double* p_db, uint32_t n) {  // link.cp
     for (uint32_t i = 0; i < n; ++i) v += (d[i] - mean) * (d[i] - mean) * p[i];
     return std::sqrt(v);
 }
+
+}  // namespace
+
+namespace dnrp::host {
 
 // link_t::set_pdp (link.cpp:66-120): profile delays scaled to tau_rms, quantised to samples (floor),
 // equal delays merged, powers normalised to 1; amplitude per tap as link.cpp:280-283
@@ -78,7 +82,7 @@ uint64_t mix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 
-bool cfg_ok(const dnrp_channel_cfg* c) {
+bool channel_cfg_ok(const dnrp_channel_cfg* c) {
     if (!c || c->kind > DNRP_CH_DOUBLY) return false;
     if (c->kind == DNRP_CH_DOUBLY && (c->pdp_idx >= PDP_N || c->samp_rate == 0 || !(c->tau_rms_ns >= 0.0f) ||
                                       c->tau_rms_ns > TAU_RMS_NS_MAX || !(c->fD_Hz >= 0.0f) || c->fD_Hz > FD_HZ_MAX))
@@ -122,13 +126,13 @@ float noise_sigma(const dnrp_channel_cfg& c) {  // noise.cpp:30-42 -> srsRAN ch_
     return std::pow(10.0f, n0_db / 20.0f) * static_cast<float>(M_SQRT1_2);
 }
 
-}  // namespace
+}  // namespace dnrp::host
 
 extern "C" {
 
 int dnrp_channel_realization(const dnrp_channel_cfg* cfg, uint32_t window, uint32_t N_TX, uint32_t N_RX, uint32_t* n_taps,
                              int32_t* delay, float* amp, int64_t* period, double* phase_rev, float* coef) {
-    if (!cfg_ok(cfg) || !n_taps || N_TX == 0 || N_RX == 0 || N_TX > 8 || N_RX > 8) return DNRP_EINVAL;
+    if (!channel_cfg_ok(cfg) || !n_taps || N_TX == 0 || N_RX == 0 || N_TX > 8 || N_RX > 8) return DNRP_EINVAL;
     std::vector<dev::channel_tap> pdp;
     if (cfg->kind == DNRP_CH_DOUBLY) set_pdp(*cfg, pdp);
     const uint32_t nl = N_RX * N_TX, nt = static_cast<uint32_t>(pdp.size());
@@ -158,7 +162,7 @@ int dnrp_channel_realization(const dnrp_channel_cfg* cfg, uint32_t window, uint3
 int dnrp_channel_batch(dnrp_ctx* ctx, const dnrp_channel_cfg* cfg, uint32_t n, uint32_t N_TX, const float* tx,
                        uint32_t S_tx, uint32_t N_RX, const int64_t* offset, const int64_t* t0, float* rx, uint32_t S_rx,
                        void* stream) {
-    if (!ctx || !cfg_ok(cfg) || (n > 0 && (!tx || !rx || !offset || !t0))) return DNRP_EINVAL;
+    if (!ctx || !channel_cfg_ok(cfg) || (n > 0 && (!tx || !rx || !offset || !t0))) return DNRP_EINVAL;
     if (n == 0) return DNRP_OK;
     if (N_TX == 0 || N_RX == 0 || N_TX > 8 || N_RX > 8 || S_tx == 0 || S_rx == 0) return DNRP_EINVAL;
     if (uint64_t(n) * N_RX > 65535u) return DNRP_ENOMEM;
@@ -201,7 +205,7 @@ int dnrp_channel_batch(dnrp_ctx* ctx, const dnrp_channel_cfg* cfg, uint32_t n, u
     a.sins = reinterpret_cast<const dev::channel_sin*>(d + b_meta + b_coef + b_taps);
     a.large_scale = cfg->large_scale;
     a.sigma = noise_sigma(*cfg);
-    a.seed = mix64(cfg->seed ^ 0x6E6F697365ull);  // "noise": independent of the link draws
+    a.seed = noise_seed(*cfg);
     if (dev::launch_channel(a, n, st) != hipSuccess) return DNRP_EDEVICE;
     return ctx->chan_tab.mark_busy(st) == hipSuccess ? DNRP_OK : DNRP_EDEVICE;
 }

@@ -325,6 +325,12 @@ struct dnrp_ctx {
     // simulated channel (channel.cpp): per-call link realisations
     dbuf chan_tab;
     pinned st_chan;
+    // virtual space (vspace.cpp): per-call emissions, tile plan and link realisations
+    dbuf vs_tab;
+    pinned st_vs;
+    // channel scanner (stream.cpp): per-call partial scans, their RMS values
+    dbuf chscan_tab, chscan_rms;
+    pinned st_chscan, st_chscan_out;
     // timing: HIP events recorded on the caller's stream around every launch (sw.timing)
     struct ev_pool {
         std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;

@@ -54,6 +54,68 @@ int dnrp_ring_gather(dnrp_ctx* ctx, const float* ring, uint64_t ring_len, uint64
     return gather(ctx, ring, ring_len, ant_stride, N_ant, n, start, S_win, out, static_cast<hipStream_t>(stream));
 }
 
+int dnrp_chscan_batch(dnrp_ctx* ctx, const float* ring, uint64_t ring_len, uint64_t ant_stride, uint32_t N_ant,
+                      uint32_t n, const dnrp_chscan_req* req, float* rms_partial, const uint32_t* partial_offset,
+                      float* rms_avg, void* stream) {
+    if (!ctx) return DNRP_EINVAL;
+    if (n == 0) return DNRP_OK;
+    if (!ring || !req || !rms_partial || !partial_offset || !rms_avg || ring_len == 0 || N_ant == 0) return DNRP_EINVAL;
+    if (N_ant > 1 && ant_stride < ring_len) return DNRP_EINVAL;
+    // chscanner_t::scan (chscanner.cpp:38-75): N_partial consecutive partial scans ending at `end`
+    uint64_t n_parts = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const auto& q = req[i];
+        // length 1 would be A == B in scan_partial, which its A < B test takes for a wrap
+        if (q.length < 2 || q.N_partial == 0 || q.N_ant == 0) return DNRP_EINVAL;
+        const uint64_t span = uint64_t(q.N_partial) * q.length;
+        if (span > ring_len || q.end < 0 || static_cast<uint64_t>(q.end) < span - 1) return DNRP_EINVAL;  // start < 0
+        n_parts += q.N_partial;
+    }
+    if (n_parts > 0x7FFFFFFFull) return DNRP_ENOMEM;
+    (void)hipSetDevice(ctx->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto* hp = static_cast<dev::chscan_part*>(ctx->st_chscan.get(sizeof(dev::chscan_part) * n_parts));
+    auto* hr = static_cast<float*>(ctx->st_chscan_out.get(sizeof(float) * n_parts));
+    if (!hp || !hr || !ctx->chscan_tab.ensure(sizeof(dev::chscan_part) * n_parts) ||
+        !ctx->chscan_rms.ensure(sizeof(float) * n_parts))
+        return DNRP_ENOMEM;
+    uint64_t k = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const auto& q = req[i];
+        const int64_t start = q.end - (int64_t(q.N_partial) * q.length - 1);
+        for (uint32_t p = 0; p < q.N_partial; ++p)
+            hp[k++] = {start + int64_t(p) * q.length, q.length, std::min(q.N_ant, N_ant)};  // chscanner.cpp:44
+    }
+    HIPCHK(ctx->chscan_tab.wait_idle(st));
+    HIPCHK(hipMemcpyAsync(ctx->chscan_tab.p, hp, sizeof(dev::chscan_part) * n_parts, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(ctx->st_chscan.ev, st));
+    dev::chscan_args a{};
+    a.ring = reinterpret_cast<const float2*>(ring);
+    a.ring_len = ring_len;
+    a.ant_stride = ant_stride;
+    a.part = ctx->chscan_tab.as<dev::chscan_part>();
+    a.rms = ctx->chscan_rms.as<float>();
+    ctx->tic("chscan", st);
+    const hipError_t le = dev::launch_chscan(a, static_cast<uint32_t>(n_parts), st);
+    ctx->toc("chscan", st);
+    if (le != hipSuccess || ctx->chscan_tab.mark_busy(st) != hipSuccess) return DNRP_EDEVICE;
+    // the square roots come from the device; the sum over a request's partial values is taken here
+    // after the copy, in float and in scan order like chscan_t::rms_avg (never divided, chscanner.cpp:63-74)
+    HIPCHK(hipMemcpyAsync(hr, ctx->chscan_rms.p, sizeof(float) * n_parts, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(ctx->st_chscan_out.ev, st));
+    HIPCHK(hipStreamSynchronize(st));
+    k = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        float sum = 0.0f;
+        for (uint32_t p = 0; p < req[i].N_partial; ++p) {
+            rms_partial[partial_offset[i] + p] = hr[k];
+            sum += hr[k++];
+        }
+        rms_avg[i] = sum;
+    }
+    return DNRP_OK;
+}
+
 int dnrp_sync_stream_init(const dnrp_ctx* ctx, const dnrp_sync_cfg* sc, dnrp_sync_stream_state* state) {
     if (!ctx || !sc || !state) return DNRP_EINVAL;
     // worker_pool_t::get_sync_time_unique_limit (worker_pool.cpp:299-321): one STF pattern of the

@@ -350,6 +350,54 @@ struct channel_args {
 };
 hipError_t launch_channel(const channel_args& a, uint32_t n, hipStream_t st);
 
+// ---- virtual space (vspace.hip): emissions superimposed into a receiver ring (vspace.cpp:449-513
+// wchannel_execute), then the simulated radio's ADC (hw_simulator.cpp:710-733)
+constexpr uint32_t VS_THREADS = 256;
+constexpr uint32_t VS_PAIRS = 2;                          // sample pairs per lane
+constexpr uint32_t VS_TILE = VS_THREADS * 2 * VS_PAIRS;   // samples of the span per workgroup
+struct vspace_em {      // one emission as the kernel reads it (32 bytes)
+    int64_t t_start;    // global time at which TX sample 0 reaches the receiver
+    uint32_t tx_row, length;
+    uint32_t slot;      // index of its link realisation in coef / taps / sins
+    uint32_t own;       // the receiver's own transmission
+    float g;            // gain * large_scale
+    uint32_t pad;
+};
+struct vspace_args {
+    uint32_t kind, N_TX, N_RX, S_tx, n_taps, n_sin;
+    const float2* tx;          // [n_rows][N_TX][S_tx]
+    float2* ring;              // antenna r at ring + r * ant_stride
+    uint64_t ring_len, ant_stride;
+    int64_t t_begin;           // global time of span sample 0
+    uint64_t n_samples;
+    const vspace_em* em;       // [n_em]
+    const uint32_t* em_off;    // [n_tiles + 1] CSR rows into em_idx: the emissions on the air in a tile, in em order
+    const uint32_t* em_idx;
+    const uint32_t* own_off;   // [n_tiles + 1] CSR rows into own_idx: the own emissions whose [t_start, t_start + length) meets it
+    const uint32_t* own_idx;
+    const float2* coef;        // flat: [slot][N_RX][N_TX]
+    const channel_tap* taps;   // doubly: [slot][N_RX][N_TX][n_taps]
+    const channel_sin* sins;   // doubly: [slot][N_RX][N_TX][n_taps][n_sin]
+    float sigma;
+    uint64_t seed;
+    float clip, step;          // ADC: clip > 0 clamps re / im to +-clip; step > 0 then rounds to multiples of step
+};
+hipError_t launch_vspace(const vspace_args& a, uint32_t n_tiles, hipStream_t st);
+
+// ---- channel scanner (ring.hip): RMS of ring spans (chscanner.cpp:77-141 scan_partial)
+struct chscan_part {
+    int64_t start;      // global time of the partial scan's first sample (>= 0)
+    uint32_t length;    // samples, <= ring_len
+    uint32_t n_ant;     // antennas 0..n_ant-1
+};
+struct chscan_args {
+    const float2* ring;
+    uint64_t ring_len, ant_stride;
+    const chscan_part* part;  // [n_parts]
+    float* rms;               // [n_parts] sqrt(energy / (length * n_ant))
+};
+hipError_t launch_chscan(const chscan_args& a, uint32_t n_parts, hipStream_t st);
+
 // ---- synchronisation (sync.hip): sync_chunk_t::search() per window, reports in search order
 struct sync_res {  // layout of dnrp_sync_result (include/dnrp.h)
     uint32_t found, det_ant;

@@ -164,12 +164,33 @@ class ChannelCfg(C.Structure):
                 ("net_bw_norm", C.c_float), ("seed", C.c_uint64)]
 
 
+class VspaceEmission(C.Structure):
+    """dnrp_vspace_emission: one transmission as the receiver's virtual space sees it (vspace.cpp:457-487)."""
+    _fields_ = [("t_start", C.c_int64), ("tx_row", C.c_uint32), ("length", C.c_uint32), ("link", C.c_uint32),
+                ("own", C.c_uint32), ("gain", C.c_float), ("reserved", C.c_uint32)]
+
+
+class AdcCfg(C.Structure):
+    """dnrp_adc_cfg: the simulated radio's clip_and_quantize (hw_simulator.cpp:710-733)."""
+    _fields_ = [("clip_limit", C.c_float), ("n_bits", C.c_uint32)]
+
+
+class ChscanReq(C.Structure):
+    """dnrp_chscan_req: one channel measurement (chscan_t): N_partial scans of `length` samples ending at `end`."""
+    _fields_ = [("end", C.c_int64), ("length", C.c_uint32), ("N_partial", C.c_uint32), ("N_ant", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    def __init__(self, end=0, length=0, N_partial=1, N_ant=0xFFFFFFFF, reserved=0):
+        super().__init__(end, length, N_partial, N_ant, reserved)  # N_ant unset: every antenna (chscanner.cpp:43)
+
+
 EXPORTS = ["dnrp_ctx_create", "dnrp_ctx_destroy", "dnrp_add_network_id", "dnrp_get_packet_sizes",
            "dnrp_compute_packet_sizes", "dnrp_tx_batch", "dnrp_rx_sync_batch",
            "dnrp_rx_pcc_batch", "dnrp_rx_pdc_batch", "dnrp_sync", "dnrp_last_kernel_ms", "dnrp_kernel_time_total",
            "dnrp_strerror", "dnrp_get_radio_device_class", "dnrp_query_param", "dnrp_param_name",
            "dnrp_ring_gather", "dnrp_sync_stream_init", "dnrp_sync_stream_window", "dnrp_rx_sync_stream",
-           "dnrp_channel_batch", "dnrp_channel_realization", "dnrp_tx_transmit_length", "dnrp_tx_packet_json",
+           "dnrp_channel_batch", "dnrp_channel_realization", "dnrp_vspace_mix", "dnrp_chscan_batch",
+           "dnrp_tx_transmit_length", "dnrp_tx_packet_json",
            "dnrp_rx_packet_json", "dnrp_crc", "dnrp_fec_cbsegm", "dnrp_fec_cb_size", "dnrp_pcc_encode",
            "dnrp_pcc_decode", "dnrp_pdc_encode", "dnrp_pdc_decode", "dnrp_harq_rx_create", "dnrp_harq_rx_reset",
            "dnrp_harq_rx_destroy", "dnrp_pdc_decode_batch", "dnrp_pdc_encode_batch",
@@ -206,6 +227,9 @@ def lib():
                                          P, C.c_uint32, P]
         L.dnrp_channel_realization.argtypes = [C.POINTER(ChannelCfg), C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.POINTER(C.c_uint32), P, P, P, P, P]
+        L.dnrp_vspace_mix.argtypes = [P, C.POINTER(ChannelCfg), C.POINTER(AdcCfg), C.c_uint32, P, C.c_uint32, P, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, P, C.c_uint64, C.c_uint64, C.c_int64, C.c_uint64, P]
+        L.dnrp_chscan_batch.argtypes = [P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, P, P, P, P, P]
         L.dnrp_tx_transmit_length.argtypes = [C.POINTER(Cfg), C.POINTER(PsDef), C.c_uint32, C.POINTER(C.c_uint32)]
         L.dnrp_tx_packet_json.argtypes = [C.POINTER(Cfg), C.POINTER(PsDef), C.POINTER(TxDesc), C.c_uint32, C.c_uint64,
                                           C.c_int64, P, P, P, C.c_uint32, C.c_char_p]
@@ -515,6 +539,58 @@ class Phy:
         _chk(lib().dnrp_channel_batch(self._ctx, C.byref(cfg), n, tx.shape[1], C.c_void_p(tx.data_ptr()), tx.shape[2],
                                       rx.shape[1], C.c_void_p(off.ctypes.data), C.c_void_p(t0.ctypes.data),
                                       C.c_void_p(rx.data_ptr()), rx.shape[2], _stream_ptr(stream)), "dnrp_channel_batch")
+
+    def vspace_mix(self, cfg, emissions, tx, ring, t_begin, n_samples, adc=None, stream=None, ring_len=None):
+        """Virtual space (dnrp_vspace_mix): the emissions (VspaceEmission list or array), their samples in
+        tx float32 [n_rows, N_TX, S_tx, 2], through the links of ChannelCfg `cfg` into global samples
+        [t_begin, t_begin + n_samples) of ring float32 [N_RX, ant_stride, 2], then noise and the ADC
+        (AdcCfg or None). ring_len: samples per ring turn when the rows are longer (default: the row)."""
+        import torch
+        dev = int(self.cfg.device)
+        n_em = len(emissions)
+        self._check_ring(ring, 1)
+        ring_len = ring.shape[1] if ring_len is None else int(ring_len)
+        if not 0 < ring_len <= ring.shape[1]:
+            raise ValueError(f"ring_len {ring_len} outside the ring rows ({ring.shape[1]} samples)")
+        if tx is None:
+            if n_em:
+                raise ValueError("vspace_mix: emissions without tx samples")
+            n_tx, n_rows, S_tx, tx_p = 1, 0, 0, None
+        else:
+            _check_tensor(tx, "tx", torch.float32, 4, dev)
+            if tx.shape[3] != 2:
+                raise ValueError(f"tx shape {tuple(tx.shape)}, expected [n_rows, N_TX, S_tx, 2]")
+            n_rows, n_tx, S_tx, tx_p = tx.shape[0], tx.shape[1], tx.shape[2], C.c_void_p(tx.data_ptr())
+        arr = emissions if isinstance(emissions, C.Array) else (VspaceEmission * n_em)(*emissions)
+        _chk(lib().dnrp_vspace_mix(self._ctx, C.byref(cfg), C.byref(adc) if adc is not None else None, n_em,
+                                   C.cast(arr, C.c_void_p) if n_em else None, n_tx, tx_p, n_rows, S_tx, ring.shape[0],
+                                   C.c_void_p(ring.data_ptr()), ring_len, ring.shape[1], int(t_begin), int(n_samples),
+                                   _stream_ptr(stream)), "dnrp_vspace_mix")
+
+    def chscan(self, ring, reqs, n_ant=None, stream=None, ring_len=None):
+        """Channel scanner (dnrp_chscan_batch, chscanner_t::scan) over ring float32 [N_ant, ant_stride, 2]:
+        returns (list of float32 arrays of the requests' partial RMS values, rms_avg float32 [n] = the
+        sum of each request's partial values, as chscan_t::rms_avg)."""
+        n_ant = n_ant or ring.shape[0]
+        self._check_ring(ring, n_ant)
+        ring_len = ring.shape[1] if ring_len is None else int(ring_len)
+        if not 0 < ring_len <= ring.shape[1]:
+            raise ValueError(f"ring_len {ring_len} outside the ring rows ({ring.shape[1]} samples)")
+        n = len(reqs)
+        arr = reqs if isinstance(reqs, C.Array) else (ChscanReq * n)(*reqs)
+        counts = np.array([arr[i].N_partial for i in range(n)], np.uint64)
+        off = np.zeros(n + 1, np.uint64)
+        np.cumsum(counts, out=off[1:])
+        if off[-1] > 0x7FFFFFFF:
+            raise ValueError("chscan: too many partial scans")
+        off32 = np.ascontiguousarray(off[:-1].astype(np.uint32))
+        part = np.zeros(max(1, int(off[-1])), np.float32)
+        avg = np.zeros(max(1, n), np.float32)
+        _chk(lib().dnrp_chscan_batch(self._ctx, C.c_void_p(ring.data_ptr()), ring_len, ring.shape[1], n_ant, n,
+                                     C.cast(arr, C.c_void_p) if n else None, C.c_void_p(part.ctypes.data),
+                                     C.c_void_p(off32.ctypes.data), C.c_void_p(avg.ctypes.data), _stream_ptr(stream)),
+             "dnrp_chscan_batch")
+        return [part[int(off[i]):int(off[i + 1])] for i in range(n)], avg[:n]
 
     def sync_stream_init(self, sc):
         state = SyncStreamState()

@@ -330,6 +330,89 @@ int dnrp_channel_batch(dnrp_ctx* ctx, const dnrp_channel_cfg* cfg, uint32_t n, u
 int dnrp_channel_realization(const dnrp_channel_cfg* cfg, uint32_t window, uint32_t N_TX, uint32_t N_RX, uint32_t* n_taps,
                              int32_t* delay, float* amp, int64_t* period, double* phase_rev, float* coef);
 
+/*
+ * Virtual space <- vspace_t::wchannel_execute (lib/src/simulation/vspace.cpp:449-513) followed by the
+ * simulated radio's clip_and_quantize (lib/src/radio/hw_simulator.cpp:686-733): the emissions of all
+ * devices, each through its own link, superimposed into one receiver's ring (the buffer_rx_t layout
+ * dnrp_ring_gather and dnrp_rx_sync_stream read: sample of global time t at index t % ring_len).
+ */
+/* One transmission as the receiver sees it (vspptx_t: tx_idx / tx_length and its samples, vspace.cpp:457-487) */
+typedef struct {
+    int64_t  t_start;   /* global hw time at which TX sample 0 of this emission reaches the receiver */
+    uint32_t tx_row;    /* row of tx [n_rows][N_TX][S_tx] holding its samples (a dnrp_tx_batch row) */
+    uint32_t length;    /* samples on the air, 1..S_tx (dnrp_tx_transmit_length) */
+    uint32_t link;      /* link realisation: dnrp_channel_realization(cfg, window = link); emissions of one
+                           device pair share it (the edge index of vspace.cpp:463-468) */
+    uint32_t own;       /* 1: the receiver's own transmission (vspace.cpp:471-487) */
+    float    gain;      /* amplitude factor of this emission's links, times cfg->large_scale
+                           (channel.cpp:53-73: db2mag(tx power - path loss or leakage - rx power)); >= 0 */
+    uint32_t reserved;  /* 0 */
+} dnrp_vspace_emission;   /* 32 bytes */
+
+/* The simulated ADC (hw_simulator_t::clip_and_quantize, hw_simulator.cpp:710-733) */
+typedef struct {
+    float    clip_limit; /* > 0: re and im clamped to +-clip_limit (clip.cpp); 0: samples pass unchanged */
+    uint32_t n_bits;     /* > 0 (with clip_limit > 0): re and im rounded to multiples of
+                            2*clip_limit / 2^n_bits, roundf (quantize.cpp, hw_simulator.cpp:710-733); <= 24 */
+} dnrp_adc_cfg;
+
+/*
+ * For every global time t in [t_begin, t_begin + n_samples) and every antenna r < N_RX the ring sample
+ * at ring + 2*(r*ant_stride + t % ring_len) floats is written exactly once; nothing is read from the
+ * ring and no other ring sample is touched. Its value (vspace.cpp:453-498, then the ADC):
+ *   s_r(t)  = sum over emissions e with own == 0, in em[] order, of gain_e * large_scale * link_e(r, x_e, t - t_start_e)
+ *   s_r(t)  = 0 where any own emission has t in [t_start, t_start + length)   (RX detached, vspace.cpp:477-479)
+ *   s_r(t) += the own emissions through their links with their gain           (leakage, vspace.cpp:487; gain 0: none)
+ *   y_r(t)  = s_r(t) + sigma * z_r(t)                                         ("relative" noise, vspace.cpp:489-498)
+ *   ring    = adc(y_r(t))          (clamp first, then roundf(y / bit_width) * bit_width; adc NULL: y_r(t))
+ * link_e is dnrp_channel_batch's per-sample link (awgn / flat / doubly of cfg->kind) with the realisation
+ * of index em[e].link; TX samples outside [0, length) are zero, the Doppler phases come from the global
+ * t, and with the doubly kind an emission reaches its largest tap delay past its length. sigma is
+ * dnrp_channel_batch's noise level; z_r(t) comes from a counter-based generator keyed by (seed, r, all
+ * 64 bits of t).
+ * Split invariance: a sample's value depends on its global time alone, never on t_begin, n_samples or
+ * how the span was tiled. Any split of a span over several calls with the same em[] therefore leaves
+ * bit-identical ring contents to one call over the whole span: a caller may fill the ring in
+ * instalments while dnrp_rx_sync_stream follows behind.
+ * An emission wholly outside the span is ignored; one that begins before it or ends after it
+ * contributes the part inside. Stream-ordered and non-blocking, like dnrp_channel_batch; n_samples == 0
+ * does nothing.
+ *   tx      device [n_rows][N_TX][S_tx] cf32 (em and tx may be NULL when n_em == 0: noise only)
+ *   ring    device cf32, antenna r at ring + 2*r*ant_stride floats; ant_stride >= ring_len >= n_samples
+ *   DNRP_EINVAL: a null pointer, N_TX / N_RX outside 1..8, t_begin or a t_start < 0, length outside
+ *   1..S_tx, tx_row >= n_rows, a negative or non-finite gain, reserved != 0, clip_limit < 0,
+ *   n_bits > 24, a configuration dnrp_channel_batch refuses.
+ */
+int dnrp_vspace_mix(dnrp_ctx* ctx, const dnrp_channel_cfg* ch, const dnrp_adc_cfg* adc /* NULL = none */,
+                    uint32_t n_em, const dnrp_vspace_emission* em, uint32_t N_TX, const float* tx,
+                    uint32_t n_rows, uint32_t S_tx, uint32_t N_RX, float* ring, uint64_t ring_len,
+                    uint64_t ant_stride, int64_t t_begin, uint64_t n_samples, void* stream);
+
+/* One channel measurement <- chscan_t (lib/include/dectnrp/phy/rx/chscan/chscan.hpp) */
+typedef struct {
+    int64_t  end;        /* global hw time of the final sample scanned (chscan_t::end_64) */
+    uint32_t length;     /* samples per partial scan, >= 2 (duration_lut of chscan_t::duration_ec, above this boundary) */
+    uint32_t N_partial;  /* partial scans, >= 1 */
+    uint32_t N_ant;      /* antennas used, clamped to the ring's N_ant (chscanner.cpp:44) */
+    uint32_t reserved;
+} dnrp_chscan_req;
+
+/*
+ * Channel scanner <- chscanner_t::scan for n requests at once (lib/src/phy/rx/chscan/chscanner.cpp:38-141)
+ * over the ring dnrp_ring_gather reads: start = end - (N_partial*length - 1), partial scan p covers global
+ * samples [start + p*length, start + (p+1)*length) with the ring's wrap, and its value
+ * sqrt(energy over the used antennas / (length * N_ant_used)) goes to rms_partial[partial_offset[i] + p]
+ * (host). rms_avg[i] (host) is what scan() leaves in chscan_t::rms_avg: the SUM of the partial values
+ * -- scan() adds them and never divides (chscanner.cpp:63-74), so a caller porting get_rms_avg() sees
+ * the same number. The square roots are taken on the device, the sums on the host after the copy.
+ * Blocking: returns after the stream's work has completed, the host arrays are then valid.
+ *   DNRP_EINVAL: a null pointer, length < 2 (scan_partial's A < B test mistakes a one-sample span for a
+ *   wrap), N_partial == 0, N_ant == 0, start < 0, N_partial*length > ring_len.
+ */
+int dnrp_chscan_batch(dnrp_ctx* ctx, const float* ring, uint64_t ring_len, uint64_t ant_stride, uint32_t N_ant,
+                      uint32_t n, const dnrp_chscan_req* req, float* rms_partial, const uint32_t* partial_offset,
+                      float* rms_avg, void* stream);
+
 /* Host only. N_samples_transmit_os_rs: the samples a radio buffer holds once the packet is complete
  * (packet without GI + GI_percentage % of the GI, tx.cpp:555-566) = the final value of the
  * reference's progressive buffer_tx_t::set_tx_length_samples_cnt (tx.cpp:241,277,292). dnrp_tx_batch
@@ -385,7 +468,7 @@ int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, floa
 
 /* Kernel timing (only when the environment has DNRP_TIMING=1 at dnrp_ctx_create): HIP events
  * recorded on the caller's stream around each launch. Names: "tx", "sync_steps", "sync_detect",
- * "sync_post", "sync_fine", "rx_stf", "rx_fft_pcc", "rx_pcc", "rx_fft_pdc", "rx_pdc". */
+ * "sync_post", "sync_fine", "rx_stf", "rx_fft_pcc", "rx_pcc", "rx_fft_pdc", "rx_pdc", "vspace_mix", "chscan". */
 int dnrp_last_kernel_ms(const dnrp_ctx* ctx, const char* name, float* ms);
 int dnrp_kernel_time_total(dnrp_ctx* ctx, const char* name, float* total_ms, uint32_t* count, int reset);
 
