@@ -246,6 +246,29 @@ int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, floa
                     v.push_back(static_cast<float>(l));
                     v.push_back(static_cast<float>(m.pdc_k[j]));
                 }
+        } else if (n == "pcc_cells") {  // (b, N_TS): per PCC cell in mapping order: symbol, subcarrier index
+            if (n_arg != 2 || !(a(0) == 1 || a(0) == 2 || a(0) == 4 || a(0) == 8 || a(0) == 12 || a(0) == 16) ||
+                !(a(1) == 1 || a(1) == 2 || a(1) == 4 || a(1) == 8))
+                return DNRP_EINVAL;
+            const auto m = geo::build_maps(a(0), a(1), a(1), 1);
+            for (uint32_t s = 0; s < m.pcc_l.size(); ++s)
+                for (uint32_t j = m.pcc_sym_off[s]; j < m.pcc_sym_off[s + 1]; ++j) {
+                    v.push_back(static_cast<float>(m.pcc_l[s]));
+                    v.push_back(static_cast<float>(m.pcc_k[j]));
+                }
+        } else if (n == "drs_cells") {  // (b, N_TS, N_DF): per DRS symbol l, ts_first, ts_last, then the
+            // N_b_OCC/4 subcarrier indices of each transmit stream ts_first..ts_last
+            if (n_arg != 3 || !(a(0) == 1 || a(0) == 2 || a(0) == 4 || a(0) == 8 || a(0) == 12 || a(0) == 16) ||
+                !(a(1) == 1 || a(1) == 2 || a(1) == 4 || a(1) == 8) || a(2) == 0 || a(2) > 1280)
+                return DNRP_EINVAL;
+            const auto m = geo::build_maps(a(0), a(1), a(1), a(2));
+            const uint32_t nd = static_cast<uint32_t>(m.drs_v.size() / 8);
+            for (const auto& d : m.drs) {
+                for (const uint32_t x : {d.l, d.ts_first, d.ts_last}) v.push_back(static_cast<float>(x));
+                for (uint32_t t = d.ts_first; t <= d.ts_last; ++t)
+                    for (uint32_t i = 0; i < nd; ++i)
+                        v.push_back(static_cast<float>(m.drs_k[(d.parity * 4 + t % 4) * nd + i]));
+            }
         } else if (n == "rx_plan_segs" || n == "rx_plan_epochs") {
             // (b, N_TS, N_eff_TX, N_DF, mode_lr, stride, twin): the PDC phase's back-end plan
             // (geo::build_rx_plan) of a transmit-diversity or single-stream packet. rx_plan_segs: per

@@ -286,6 +286,34 @@ def query_table(name, *args):
     return out[:n]
 
 
+def pcc_cells(b, N_TS):
+    """Host-only: the 98 PCC cells in mapping order as int rows (l, k) (dnrp_query_table "pcc_cells")."""
+    return query_table("pcc_cells", b, N_TS).astype(np.int64).reshape(-1, 2)
+
+
+def pdc_cells(b, N_TS, N_DF):
+    """Host-only: the PDC cells of a packet with N_DF data-field symbols in mapping order as int rows (l, k)
+    (dnrp_query_table "pdc_cells")."""
+    return query_table("pdc_cells", b, N_TS, N_TS, N_DF).astype(np.int64).reshape(-1, 2)
+
+
+def symbol_cells(b, N_TS, N_DF):
+    """Host-only: int rows (PCC, PDC, DRS cell count) of symbols l = 0..N_DF (dnrp_query_table "symbol_cells")."""
+    return query_table("symbol_cells", b, N_TS, N_TS, N_DF).astype(np.int64).reshape(-1, 3)
+
+
+def drs_cells(b, N_TS, N_DF):
+    """Host-only: the DRS symbols of a packet as a list of (l, ts_first, ts_last, k [streams, N_b_OCC/4])
+    (dnrp_query_table "drs_cells")."""
+    v, nd, out, i = query_table("drs_cells", b, N_TS, N_DF).astype(np.int64), 14 * b, [], 0
+    while i < len(v):
+        l, first, last = (int(x) for x in v[i:i + 3])
+        n = (last - first + 1) * nd
+        out.append((l, first, last, v[i + 3:i + 3 + n].reshape(-1, nd)))
+        i += 3 + n
+    return out
+
+
 def channel_realization(cfg, window, n_tx, n_rx):
     """Host-only: window `window`'s link realisation of a ChannelCfg (dnrp_channel_realization):
     dict with delay / amp [n_rx, n_tx, taps], period / phase_rev [n_rx, n_tx, taps, 40], coef [n_rx, n_tx]."""

@@ -461,6 +461,12 @@ const char* dnrp_param_name(uint32_t index);
  *   "stf_cover_sequence" ()      stf_t::cover_sequence (stf.hpp:146-151)
  *   "cells_lds_bytes" (u_max, b_max, b, N_RX, N_eff_TX)   LDS bytes of the PDC equaliser's staging for
  *                                the geometry; above 160 KiB dnrp_rx_*_batch return DNRP_EUNSUPPORTED
+ *   "symbol_cells" (b, N_TS, N_eff_TX, N_DF)   per symbol l = 0..N_DF the number of PCC, PDC and DRS cells
+ *   "pdc_cells" (b, N_TS, N_eff_TX, N_DF)   per PDC cell in mapping order: symbol l, subcarrier index k
+ *                                (pdc.cpp:108-153; k counts from the lowest occupied subcarrier, DC included)
+ *   "pcc_cells" (b, N_TS)        per PCC cell in mapping order: symbol l, subcarrier index k (pcc.cpp:83-108)
+ *   "drs_cells" (b, N_TS, N_DF)  per DRS symbol: l, ts_first, ts_last, then the N_b_OCC/4 subcarrier
+ *                                indices k of each transmit stream ts_first..ts_last (drs.cpp:73-125)
  *   "rx_epoch_syms" (b, N_TS, N_eff_TX, N_DF, mode_lr, stride)   the epoch receiver's symbol ownership of
  *                                the PDC phase: ok (0 / 1), per plan epoch its symbol count and symbols,
  *                                then the DRS-pass symbols */

@@ -8,13 +8,16 @@
 // Pinning status:
 //   * pinned against the reference's own compiled sources (oracle/_ref, built by
 //     oracle/Makefile from /root/reference): numerologies, tm_mode, mcs, transport block size,
-//     packet structure lengths, Kaiser resampler taps, Bessel/sinc channel statistics.
+//     packet structure lengths, Kaiser resampler taps, Bessel/sinc channel statistics; the
+//     DRS/PCC/PDC cell maps, DRS values, W and the pdc_t packet counts (drs.cpp, pcc.cpp, pdc.cpp and
+//     beamforming_and_antenna_port_mapping.cpp compiled with ref_standin/srsran/config.h, our own
+//     one-typedef stand-in; tests/test_cell_pins.py).
 //   * pinned against SURVEY.md §8 numbers produced from the reference sources:
 //     N_PDC_subc / G / N_TB for the benchmark configurations.
 //   * parity unpinned (srsRAN semantics absent from the image, restated from 3GPP TS 36.211 /
 //     srsRAN release_23_11 behaviour): LTE constellation tables, int16 soft demapper scale and
-//     rounding, Gold sequence; the STF/DRS/PCC/PDC cell maps are restated from the reference's
-//     sections_part3 code (which cannot be compiled here without srsRAN headers).
+//     rounding, Gold sequence; the STF values are restated from the reference's stf.cpp (which
+//     needs VOLK) and pinned to its literals only (tests/test_literal_pins.py).
 #pragma once
 
 #include <complex>

@@ -230,6 +230,25 @@ int oracle_pcc_cells(uint32_t b, uint32_t N_TS, uint32_t* out_l, uint32_t* out_k
     return static_cast<int>(o);
 }
 
+// DRS symbols of a packet as the TX and RX walk them (drs_schedule + drs_k_i): per symbol l, ts_first,
+// ts_last, then the N_b_OCC/4 indices of each stream ts_first..ts_last. Returns the number of words
+// (out may be null to ask for it), -1 if cap is too small
+int oracle_drs_cells(uint32_t b, uint32_t N_TS, uint32_t N_DF, uint32_t* out, uint32_t cap) {
+    std::vector<uint32_t> v;
+    for (const auto& s : drs_schedule(N_TS, N_DF)) {
+        v.insert(v.end(), {s.l, s.ts_first, s.ts_last});
+        for (uint32_t t = s.ts_first; t <= s.ts_last; ++t) {
+            const auto k = drs_k_i(b, t % 4, s.k_parity);
+            v.insert(v.end(), k.begin(), k.end());
+        }
+    }
+    if (out) {
+        if (cap < v.size()) return -1;
+        std::memcpy(out, v.data(), v.size() * sizeof(uint32_t));
+    }
+    return static_cast<int>(v.size());
+}
+
 // LUT export: returns number of weight vectors; idx arrays sized T*4*(56b+1)
 int oracle_chest_lut(uint32_t Nsv, uint32_t b, uint32_t b_max, uint32_t u_max, uint32_t profile,
                      uint32_t* idx_pilot, uint32_t* idx_weight, float* weights, uint32_t max_w) {

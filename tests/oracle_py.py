@@ -44,6 +44,7 @@ def lib():
         L.oracle_stf.argtypes = [C.c_uint32, C.c_uint32, F64P]
         L.oracle_pdc_cells.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, U32P, U32P]
         L.oracle_pcc_cells.argtypes = [C.c_uint32, C.c_uint32, U32P, U32P]
+        L.oracle_drs_cells.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
         L.oracle_chest_lut.argtypes = [C.c_uint32] * 5 + [U32P, U32P, F32P, C.c_uint32]
         L.oracle_tx.argtypes = [U32P, U32P, U32P, F64P, U8P, U8P, F32P, C.c_uint32, C.c_int]
         L.oracle_rx.argtypes = [U32P, U32P, C.c_uint32, F32P, C.c_uint32, C.c_int64, C.c_double, C.c_uint32,
@@ -232,6 +233,35 @@ def stf(b, n_eff_tx):
 def drs_values(b, t):
     out = np.zeros(14 * b)
     return out[: lib().oracle_drs_values(b, t, out)]
+
+
+def pcc_cells(b, N_TS):
+    """the 98 PCC cells in mapping order as int rows (l, k)"""
+    l, k = np.zeros(98, np.uint32), np.zeros(98, np.uint32)
+    n = lib().oracle_pcc_cells(b, N_TS, l, k)
+    return np.stack([l[:n], k[:n]], axis=1).astype(np.int64)
+
+
+def pdc_cells(b, N_TS, N_DF):
+    """per symbol l = 0..N_DF the PDC subcarrier indices in mapping order (list of int arrays)"""
+    cnt, k = np.zeros(N_DF + 1, np.uint32), np.zeros((N_DF + 1) * 56 * b, np.uint32)
+    n = lib().oracle_pdc_cells(b, N_TS, N_DF, cnt, k)
+    assert n == int(cnt.sum())
+    return np.split(k[:n].astype(np.int64), np.cumsum(cnt)[:-1])
+
+
+def drs_cells(b, N_TS, N_DF):
+    """the DRS symbols of a packet as a list of (l, ts_first, ts_last, k [streams, N_b_OCC/4])"""
+    n = lib().oracle_drs_cells(b, N_TS, N_DF, None, 0)
+    v = np.zeros(max(1, n), np.uint32)
+    assert lib().oracle_drs_cells(b, N_TS, N_DF, v.ctypes.data, n) == n
+    v, nd, out, i = v[:n].astype(np.int64), 14 * b, [], 0
+    while i < n:
+        l, first, last = (int(x) for x in v[i:i + 3])
+        m = (last - first + 1) * nd
+        out.append((l, first, last, v[i + 3:i + 3 + m].reshape(-1, nd)))
+        i += 3 + m
+    return out
 
 
 def txdiv_pairs(N_TS):
