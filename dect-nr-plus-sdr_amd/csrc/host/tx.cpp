@@ -4,6 +4,45 @@
 using namespace dnrp;
 using namespace dnrp::host;
 
+namespace {
+
+// Window length of an N_b_DFT_os-point symbol (dft/windowing.cpp:34-39 with tx.cpp:71-77): the
+// data-field cyclic prefix N_b_DFT_os / 8 times the fraction, rounded in float; 0: no valid window
+uint32_t window_length(uint32_t N_b_DFT_os, float fraction) {
+    if (N_b_DFT_os == 0 || N_b_DFT_os % 8 != 0 || !(fraction > 0.0f && fraction <= 1.0f)) return 0;
+    const uint32_t N = static_cast<uint32_t>(std::round(static_cast<float>(N_b_DFT_os / 8) * fraction));
+    return N >= 2 ? N : 0;
+}
+
+// rising edge (filter/raised_cosine.cpp:30-56), float arithmetic in the reference's order
+std::vector<float> window_rising(uint32_t N) {
+    std::vector<float> rc(N);
+    const float N_f = static_cast<float>(N), pi_f = 3.14159265358979323846f;
+    for (uint32_t n = 0; n < N; ++n) {
+        const float A = std::cos((static_cast<float>(n) - N_f) / N_f * pi_f * 0.5f);
+        rc[n] = A * A;
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int dnrp_ctx_set_tx_windowing(dnrp_ctx* ctx, float fraction) {
+    if (!ctx || !(fraction >= 0.0f && fraction <= 1.0f)) return DNRP_EINVAL;  // NaN fails both comparisons
+    ctx->tx_win_fraction = fraction;
+    return DNRP_OK;
+}
+
+extern "C" int dnrp_tx_window(uint32_t N_b_DFT_os, float fraction, float* rising, uint32_t cap) {
+    const uint32_t N = window_length(N_b_DFT_os, fraction);
+    if (N == 0) return DNRP_EINVAL;
+    if (!rising) return static_cast<int>(N);
+    if (cap < N) return DNRP_EINVAL;
+    const auto rc = window_rising(N);
+    std::memcpy(rising, rc.data(), N * sizeof(float));
+    return static_cast<int>(N);
+}
+
 extern "C" int dnrp_tx_batch(dnrp_ctx* ctx, const dnrp_psdef* psdef, uint32_t n, const dnrp_tx_desc* desc, const uint8_t* pcc_d,
                   const uint8_t* pdc_d, uint32_t pdc_stride, float* iq_out, uint32_t S, void* stream) {
     if (!ctx || !psdef || (n > 0 && (!desc || !pcc_d || !pdc_d || !iq_out))) return DNRP_EINVAL;
@@ -16,6 +55,26 @@ extern "C" int dnrp_tx_batch(dnrp_ctx* ctx, const dnrp_psdef* psdef, uint32_t n,
     if (!t) return err;
     if (S < t->dm.N_packet_rs || pdc_stride < (t->q.G + 7) / 8) return DNRP_EINVAL;
     if (t->q.N_b_OCC + 1 > 1024) return DNRP_EUNSUPPORTED;
+    // OFDM windowing (dnrp_ctx_set_tx_windowing): the packet's window, checked before anything is
+    // queued -- the reference asserts 2 <= N (dft/windowing.cpp:39)
+    uint32_t win_n = 0;
+    const float* win = nullptr;
+    if (ctx->tx_win_fraction > 0.0f) {
+        win_n = window_length(t->dm.Nd, ctx->tx_win_fraction);
+        if (win_n == 0) return t->dm.Nd % 8 ? DNRP_EUNSUPPORTED : DNRP_EINVAL;
+        // tx.hip tx_window_run leaves the prefix of a run's history symbol unshaped: the resampler
+        // history must end behind it
+        if (win_n > t->dm.CP || t->rs.hl + win_n >= t->dm.CP + t->dm.Nd) return DNRP_EUNSUPPORTED;
+        uint32_t fbits;
+        std::memcpy(&fbits, &ctx->tx_win_fraction, sizeof fbits);
+        auto& wb = ctx->tx_win[{t->dm.Nd, fbits}];
+        if (!wb) {
+            auto nb = std::make_unique<dbuf>();
+            if (!nb->upload(window_rising(win_n))) return DNRP_ENOMEM;
+            wb = std::move(nb);
+        }
+        win = wb->as<float>();
+    }
     auto* pk = static_cast<dev::tx_pkt*>(ctx->st_tx.get(sizeof(dev::tx_pkt) * n));
     if (!pk) return DNRP_ENOMEM;
     for (uint32_t i = 0; i < n; ++i) {
@@ -121,7 +180,10 @@ extern "C" int dnrp_tx_batch(dnrp_ctx* ctx, const dnrp_psdef* psdef, uint32_t n,
     a.pdc_d = pdc_d;
     a.out = iq_out;
     a.pk = ctx->tx_pk.as<dev::tx_pkt>();
-    // streaming kernel (tx.hip tx_stream_kernel) where its geometry holds
+    a.win = win;
+    a.win_n = win_n;
+    // streaming kernel (tx.hip tx_stream_kernel) where its geometry holds (its windowed form holds a
+    // window of up to CP = 128 samples)
     a.stream = 0;
     if (wave && t->code_bin.p && dev::tx_stream_taps_match(t->rs.h.data(), t->rs.h.size()) && a.L == 10 && a.M == 9 && a.hl == 22 && a.CP == 128 && a.STF_CP == 1280 &&
         a.pattern_len * 9 == a.STF_CP + 1024 && S % 2 == 0 && (reinterpret_cast<uintptr_t>(iq_out) & 15u) == 0) {

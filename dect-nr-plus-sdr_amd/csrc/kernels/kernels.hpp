@@ -77,6 +77,10 @@ struct tx_args {
     float2* big;
     uint32_t big_len;
     uint32_t big_batch;  // packets per scratch pass (the scratch holds big_batch x N_TX rows)
+    // OFDM windowing (PHY_TX_OFDM_WINDOWING, tx.cpp:881-908): rising raised-cosine edge of win_n <= CP
+    // samples (dnrp_tx_window), the falling edge is its mirror; win_n = 0: off (the default kernels)
+    const float* win;
+    uint32_t win_n;
 };
 hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st);
 bool tx_stream_taps_match(const float* h, size_t n);  // compiled-in 10/9 taps == run-time taps

@@ -15,6 +15,8 @@
 // stf_t::apply_cover_sequence (sections_part3/stf.cpp:104-138), resampler_t (resampler.cpp:330-454)
 // and mixer_t::mix_phase_continuous (mixer.cpp:41-65). Only the packed d-bits are read and only
 // the final hw-rate IQ is written: HBM traffic = ceil(G/8) + 25 bytes in, N_TX * S * 8 bytes out.
+// With OFDM windowing on (tx_args::win_n, PHY_TX_OFDM_WINDOWING: tx.cpp:881-908) the WIN instantiations
+// of the run kernels shape the symbol transitions in the LDS buffer ahead of the resampler.
 #include "device_common.hpp"
 #include "experiments.hpp"
 #include "kernels.hpp"
@@ -270,6 +272,37 @@ __device__ __forceinline__ void tx_zero_pads(const tx_wg& w) {
     for (uint32_t i = data_end + threadIdx.x; i < w.A->lin_len; i += blockDim.x) w.lin[i] = make_float2(0.f, 0.f);
 }
 
+// OFDM windowing (PHY_TX_OFDM_WINDOWING: tx.cpp:881-908, dft/windowing.cpp:34-56), one sample of it:
+// the first win_n samples of a data-field symbol's cyclic prefix fade in with the rising edge and
+// overlap the cyclic continuation of the symbol before it -- the first win_n samples of that symbol's
+// body -- faded out with the mirrored edge. A product and a sum as two roundings, like the reference's
+// multiply and add calls. prev: body sample n of symbol l - 1, which the kernels hold STF-covered;
+// the reference stashes the STF ahead of its cover sequence (tx.cpp:226-234), so for l = 1 the
+// pattern's sign is undone (+-1: the same product again)
+__device__ __forceinline__ float2 tx_window_sample(const tx_args& A, uint32_t l, uint32_t n, float2 cp, float2 prev) {
+    if (l == 1) prev = cscale(prev, k_cover[min((A.STF_CP + n) / A.pattern_len, 8u)]);
+    const float up = A.win[n], dn = A.win[A.win_n - 1 - n];
+    return make_float2(__fadd_rn(__fmul_rn(cp.x, up), __fmul_rn(prev.x, dn)),
+                       __fadd_rn(__fmul_rn(cp.y, up), __fmul_rn(prev.y, dn)));
+}
+
+// the run's symbols max(l_first, 1)..l_last in the linear LDS buffer, between the IFFT stores and the
+// resampler. The symbol before the run's first is the history symbol s0, whole in the buffer; its own
+// prefix stays unshaped (the resampler reads its last hl samples only: host-checked). Reads (symbol
+// l - 1 from its prefix length on) and writes (symbol l below win_n <= CP) are disjoint, so one barrier
+// ahead of the pass and one after it order it
+__device__ __forceinline__ void tx_window_run(const tx_wg& w) {
+    const tx_args& A = *w.A;
+    const uint32_t l0 = max(w.l_first, 1u);
+    if (l0 > w.l_last) return;
+    const uint32_t cnt = (w.l_last - l0 + 1) * A.win_n;
+    for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) {
+        const uint32_t l = l0 + i / A.win_n, n = i % A.win_n;
+        float2* cp = w.slot(l);
+        cp[n] = tx_window_sample(A, l, n, cp[n], w.slot(l - 1)[(l == 1 ? A.STF_CP : A.CP) + n]);
+    }
+}
+
 // resample + mix every output whose newest input lies in the run (the last run adds the flush
 // samples) and store it; GI / slot tail zeros on the last run (tx.cpp:679-714)
 template <int LR, int MR, int HLR>
@@ -387,7 +420,9 @@ __device__ __forceinline__ void tx_resample(const tx_wg& w) {
 }
 
 // ---- N_b_DFT_os = 1024: wavefront b owns slot b (symbol s0 + b)
-template <int LR, int MR, int HLR>
+// WIN: the OFDM windowing pass (tx_window_run) -- an instantiation of its own, so the default kernel
+// carries none of it
+template <int LR, int MR, int HLR, bool WIN>
 __global__ void __launch_bounds__(TX_WAVE_MAX) tx_kernel_wave(tx_args A) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     uint32_t rc[16];  // cell codes of the wave's 16 bins per lane, loaded with the staging
@@ -406,6 +441,10 @@ __global__ void __launch_bounds__(TX_WAVE_MAX) tx_kernel_wave(tx_args A) {
         w.put_symbol(l, v, lane);
     }
     __syncthreads();
+    if constexpr (WIN) {
+        tx_window_run(w);
+        __syncthreads();
+    }
     tx_resample<LR, MR, HLR>(w);
 }
 
@@ -657,7 +696,22 @@ __device__ __forceinline__ void txs_emit(const float2* buf, __amdgpu_buffer_rsrc
     }
 }
 
-template <int LR, int MR, int HLR, int MODE, bool Q8, int MF>
+// WIN: OFDM windowing (tx_window_sample's arithmetic). A wave sees one symbol at a time, so it carries
+// the stash of the symbol before -- body samples lane and lane + 64, which are v[0] and v[1] of that
+// symbol's FFT, times the falling edge -- in four registers from piece to piece; the STF's come from
+// the FFT output ahead of the cover sequence, as the reference takes them (tx.cpp:226-234). The rising
+// edge sits in LDS behind the waves' buffers, padded with 1 to the prefix length (the workgroup's
+// 512 B more keep four workgroups per CU). A segment's history piece has no stash of its own
+// predecessor: its prefix comes out unshaped, and only its last TXS_CARRY samples are read.
+constexpr uint32_t TXS_WIN = 128;  // window table entries = CP
+template <bool WIN>
+struct txs_stash {  // the stash of the symbol before, samples lane and lane + 64; tab: the edge in LDS
+    float2 s0, s1;
+    const float* tab;
+};
+template <>
+struct txs_stash<false> {};  // the default kernel declares nothing
+template <int LR, int MR, int HLR, int MODE, bool Q8, int MF, bool WIN>
 #ifndef DNRP_TX_IMAJ
 #define DNRP_TX_IMAJ 0  // 1: the polyphase windows input-major from LDS (pp_const::run_imaj; 96 VGPRs against
                         // 120 at the same LDS-bound 16 waves per CU): TX 17.13 / 17.07 vs 16.99 / 16.99 ms, off
@@ -692,6 +746,13 @@ __global__ void __launch_bounds__(64 * TXS_WPG) __attribute__((amdgpu_waves_per_
     T.qlev = reinterpret_cast<float*>(qtab);
     T.buf = smem + 256 + wv * (TXS_BUF + TXS_WROW);
     T.wrow = T.buf + TXS_BUF;
+    txs_stash<WIN> ws;
+    if constexpr (WIN) {
+        float* wtab = reinterpret_cast<float*>(smem + 256 + TXS_WPG * (TXS_BUF + TXS_WROW));  // [TXS_WIN]
+        for (uint32_t i = threadIdx.x; i < TXS_WIN; i += blockDim.x) wtab[i] = i < A.win_n ? A.win[i] : 1.f;
+        ws.tab = wtab;
+        ws.s0 = ws.s1 = make_float2(0.f, 0.f);
+    }
     const uint32_t gw = blockIdx.x * TXS_WPG + wv;
     T.ant = gw % A.N_TX;
     const uint32_t seg = (gw / A.N_TX) % A.n_seg;
@@ -853,7 +914,16 @@ __global__ void __launch_bounds__(64 * TXS_WPG) __attribute__((amdgpu_waves_per_
                 for (int m = 0; m < 16; ++m) {
                     const float2 sv = txs_slot<MF>(v[m]);
                     buf[TXS_CARRY + 128 + lid + 64 * m] = sv;
-                    if (m >= 14) buf[TXS_CARRY + lid + 64 * (m - 14)] = sv;
+                    if constexpr (WIN) {
+                        if (m >= 14) {  // prefix sample lid + 64 (m - 14): rising edge (1 beyond the window) + stash
+                            const float up = ws.tab[lid + 64 * (m - 14)];
+                            const float2 st = m == 14 ? ws.s0 : ws.s1;
+                            buf[TXS_CARRY + lid + 64 * (m - 14)] = txs_slot<MF>(make_float2(
+                                __fadd_rn(__fmul_rn(v[m].x, up), st.x), __fadd_rn(__fmul_rn(v[m].y, up), st.y)));
+                        }
+                    } else {
+                        if (m >= 14) buf[TXS_CARRY + lid + 64 * (m - 14)] = sv;
+                    }
                 }
             } else {  // STF (CP 1280, covered): piece r holds samples [1152 r, 1152 r + 1152)
                 const uint32_t cp = A.STF_CP, len = cp + 1024, i0 = r == 1 ? TXS_PIECE : 0u;
@@ -863,6 +933,13 @@ __global__ void __launch_bounds__(64 * TXS_WPG) __attribute__((amdgpu_waves_per_
                     for (uint32_t i = (nn + cp) & 1023u; i < len; i += 1024)
                         if (i - i0 < TXS_PIECE) buf[TXS_CARRY + i - i0] = txs_slot<MF>(cscale(v[m], cover_sign(min(i / A.pattern_len, 8u))));
                 }
+            }
+            if constexpr (WIN) {  // this symbol's stash: body samples lid, lid + 64 times the falling edge (0 beyond it)
+                const uint32_t c1 = lid + 64;
+                const float dn0 = lid < A.win_n ? ws.tab[min(A.win_n - 1 - lid, TXS_WIN - 1)] : 0.f;
+                const float dn1 = c1 < A.win_n ? ws.tab[min(A.win_n - 1 - c1, TXS_WIN - 1)] : 0.f;
+                ws.s0 = make_float2(__fmul_rn(v[0].x, dn0), __fmul_rn(v[0].y, dn0));
+                ws.s1 = make_float2(__fmul_rn(v[1].x, dn1), __fmul_rn(v[1].y, dn1));
             }
         } else {
             for (uint32_t i = lid; i < TXS_PIECE; i += 64) buf[TXS_CARRY + i] = make_float2(0.f, 0.f);
@@ -1007,10 +1084,12 @@ bool tx_stream_taps_match(const float* h, size_t n) {  // run-time taps == compi
     return true;
 }
 
-size_t tx_stream_lds() { return (256 + TXS_WPG * (TXS_BUF + TXS_WROW)) * sizeof(float2); }
+size_t tx_stream_lds(bool win) {
+    return (256 + TXS_WPG * (TXS_BUF + TXS_WROW)) * sizeof(float2) + (win ? TXS_WIN * sizeof(float) : 0);
+}
 
 // ---- other FFT sizes: workgroup-wide batched Stockham FFT
-template <int LR, int MR, int HLR>
+template <int LR, int MR, int HLR, bool WIN>
 __global__ void __launch_bounds__(TX_THREADS) tx_kernel(tx_args A) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     const tx_wg w = tx_setup<false>(A, smem);
@@ -1042,6 +1121,10 @@ __global__ void __launch_bounds__(TX_THREADS) tx_kernel(tx_args A) {
     // the IFFT used the whole of lin as scratch: pads are zeroed after it
     tx_zero_pads(w);
     __syncthreads();
+    if constexpr (WIN) {
+        tx_window_run(w);
+        __syncthreads();
+    }
     tx_resample<LR, MR, HLR>(w);
 }
 
@@ -1101,6 +1184,22 @@ __global__ void __launch_bounds__(TX_BIG_THREADS) tx_big_sym_kernel(tx_args A) {
     });
 }
 
+// OFDM windowing of the scratch rows, in place between the two kernels: one thread per (packet,
+// antenna, symbol l >= 1, n < win_n). A row's reads (bodies, from a prefix length on) and writes
+// (prefixes below win_n <= CP) are disjoint, so the threads need no order among them
+__global__ void __launch_bounds__(256) tx_big_window_kernel(tx_args A, uint32_t rows) {
+    const uint32_t per = A.N_DF * A.win_n;
+    const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= uint64_t(rows) * per) return;
+    const uint32_t pa = static_cast<uint32_t>(i / per), r = static_cast<uint32_t>(i % per);
+    const uint32_t l = 1 + r / A.win_n, n = r % A.win_n;
+    const uint32_t len0 = A.STF_CP + A.plan.N, lenD = A.CP + A.plan.N;
+    float2* x = A.big + size_t(pa) * A.big_len;
+    float2* cp = x + len0 + size_t(l - 1) * lenD;                                  // symbol l
+    const float2* body = l == 1 ? x + A.STF_CP : cp - lenD + A.CP;  // symbol l - 1 behind its prefix
+    cp[n] = tx_window_sample(A, l, n, cp[n], body[n]);
+}
+
 // grid: (packet, antenna) x output blocks folded into x (gridDim.y is capped at 65536 rows)
 __global__ void __launch_bounds__(256) tx_big_resample_kernel(tx_args A, uint32_t total) {
     const uint32_t nb = (A.S + 255) / 256;
@@ -1140,15 +1239,23 @@ size_t tx_lds_bytes(const tx_args& a) {
 }
 
 hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st) {
+    // windowing: a table of 2 <= win_n <= CP entries
+    if (a.win_n && (!a.win || a.win_n < 2 || a.win_n > a.CP)) return hipErrorInvalidValue;
     if (a.stream) {
         const uint64_t waves = uint64_t(n) * a.N_TX * a.n_seg;
         const dim3 g(static_cast<uint32_t>((waves + TXS_WPG - 1) / TXS_WPG)), b(64 * TXS_WPG);
         const int mode = a.N_TS == 1 ? TXS_SISO : a.txdiv ? (a.onehot ? TXS_TXDIV1 : TXS_TXDIV) : (a.onehot ? TXS_SM1 : TXS_SM);
-#define DNRP_TXS(MODE, Q8)                                                                                       \
-    do {                                                                                                         \
-        if (a.mfma == 2) hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 2>), g, b, tx_stream_lds(), st, a, n); \
-        else if (a.mfma) hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 1>), g, b, tx_stream_lds(), st, a, n); \
-        else hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 0>), g, b, tx_stream_lds(), st, a, n);      \
+        if (a.win_n > TXS_WIN) return hipErrorInvalidValue;
+#define DNRP_TXS_W(MODE, Q8, WIN)                                                                                           \
+    do {                                                                                                                    \
+        if (a.mfma == 2) hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 2, WIN>), g, b, tx_stream_lds(WIN), st, a, n); \
+        else if (a.mfma) hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 1, WIN>), g, b, tx_stream_lds(WIN), st, a, n); \
+        else hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 0, WIN>), g, b, tx_stream_lds(WIN), st, a, n);      \
+    } while (0)
+#define DNRP_TXS(MODE, Q8)                          \
+    do {                                            \
+        if (a.win_n) DNRP_TXS_W(MODE, Q8, true);    \
+        else DNRP_TXS_W(MODE, Q8, false);           \
     } while (0)
         if (a.N_bps == 8) {
             if (mode == TXS_SISO) DNRP_TXS(TXS_SISO, true);
@@ -1164,6 +1271,7 @@ hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st) {
             else DNRP_TXS(TXS_SM, false);
         }
 #undef DNRP_TXS
+#undef DNRP_TXS_W
         return hipGetLastError();
     }
     if (a.big) {
@@ -1179,6 +1287,8 @@ hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st) {
         if (uint64_t((a.S + 255) / 256) * np_max * a.N_TX > 0x7FFFFFFFull ||
             np_max * a.N_TX * (a.N_DF + 1) > 0x7FFFFFFFull)
             return hipErrorInvalidValue;
+        const uint64_t win_per = uint64_t(a.N_DF) * a.win_n;  // windowed samples per scratch row
+        if ((np_max * a.N_TX * win_per + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
         for (uint32_t p0 = 0; p0 < n; p0 += a.big_batch) {
             const uint32_t np = min(a.big_batch, n - p0);
             tx_args b = a;
@@ -1188,6 +1298,9 @@ hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st) {
             b.out = a.out + size_t(p0) * a.N_TX * a.S * 2;
             const uint64_t gx = uint64_t((a.S + 255) / 256) * np * a.N_TX;
             hipLaunchKernelGGL(tx_big_sym_kernel, dim3(np * a.N_TX * (a.N_DF + 1)), dim3(TX_BIG_THREADS), lds, st, b);
+            if (win_per)
+                hipLaunchKernelGGL(tx_big_window_kernel, dim3(static_cast<uint32_t>((uint64_t(np) * a.N_TX * win_per + 255) / 256)),
+                                   dim3(256), 0, st, b, np * a.N_TX);
             hipLaunchKernelGGL(tx_big_resample_kernel, dim3(static_cast<uint32_t>(gx)), dim3(256), 0, st, b, total);
         }
         return hipGetLastError();
@@ -1199,10 +1312,14 @@ hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st) {
     const dim3 g(n * a.N_TX * a.n_runs), b(wave ? 64 * (a.K + 1) : TX_THREADS);
 #define DNRP_TX_LAUNCH(LR, MR, HLR)                                                      \
     do {                                                                                 \
-        if (wave)                                                                        \
-            hipLaunchKernelGGL((tx_kernel_wave<LR, MR, HLR>), g, b, lds, st, a);         \
+        if (wave && a.win_n)                                                             \
+            hipLaunchKernelGGL((tx_kernel_wave<LR, MR, HLR, true>), g, b, lds, st, a);   \
+        else if (wave)                                                                   \
+            hipLaunchKernelGGL((tx_kernel_wave<LR, MR, HLR, false>), g, b, lds, st, a);  \
+        else if (a.win_n)                                                                \
+            hipLaunchKernelGGL((tx_kernel<LR, MR, HLR, true>), g, b, lds, st, a);        \
         else                                                                             \
-            hipLaunchKernelGGL((tx_kernel<LR, MR, HLR>), g, b, lds, st, a);              \
+            hipLaunchKernelGGL((tx_kernel<LR, MR, HLR, false>), g, b, lds, st, a);       \
     } while (0)
     if (a.L == 10 && a.M == 9 && a.hl == 22)  // os_min 1 (223 taps)
         DNRP_TX_LAUNCH(10, 9, 22);

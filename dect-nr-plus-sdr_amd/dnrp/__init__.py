@@ -195,7 +195,8 @@ EXPORTS = ["dnrp_ctx_create", "dnrp_ctx_destroy", "dnrp_add_network_id", "dnrp_g
            "dnrp_pcc_decode", "dnrp_pdc_encode", "dnrp_pdc_decode", "dnrp_harq_rx_create", "dnrp_harq_rx_reset",
            "dnrp_harq_rx_destroy", "dnrp_pdc_decode_batch", "dnrp_pdc_encode_batch",
            "dnrp_pcc_decode_batch", "dnrp_pdc_decode_batch_harq", "dnrp_pdc_softbuffer_size",
-           "dnrp_pcc_encode_batch", "dnrp_query_table", "dnrp_ctx_set_rx_mode"]
+           "dnrp_pcc_encode_batch", "dnrp_query_table", "dnrp_ctx_set_rx_mode", "dnrp_ctx_set_tx_windowing",
+           "dnrp_tx_window"]
 
 _lib = None
 
@@ -222,6 +223,8 @@ def lib():
                                         C.POINTER(PdcReport), P]
         L.dnrp_sync.argtypes = [P, P]
         L.dnrp_ctx_set_rx_mode.argtypes = [P, C.c_uint32]
+        L.dnrp_ctx_set_tx_windowing.argtypes = [P, C.c_float]
+        L.dnrp_tx_window.argtypes = [C.c_uint32, C.c_float, P, C.c_uint32]
         L.dnrp_ring_gather.argtypes = [P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, P, C.c_uint32, P, P]
         L.dnrp_channel_batch.argtypes = [P, C.POINTER(ChannelCfg), C.c_uint32, C.c_uint32, P, C.c_uint32, C.c_uint32, P, P,
                                          P, C.c_uint32, P]
@@ -270,6 +273,17 @@ def compute_packet_sizes(ps, u_max=None, b_max=None, os_min=1, L=10, M=9):
     if rc != 0:
         raise DnrpError(rc, "dnrp_compute_packet_sizes")
     return out.as_dict()
+
+
+def tx_window(N_b_DFT_os, fraction):
+    """Host-only: the rising raised-cosine edge of TX OFDM windowing (dnrp_tx_window) for an N_b_DFT_os-point
+    symbol at `fraction` as a float32 array of the window length N; the falling edge is its mirror."""
+    n = lib().dnrp_tx_window(int(N_b_DFT_os), float(fraction), None, 0)
+    if n < 0:
+        raise DnrpError(n, f"dnrp_tx_window({N_b_DFT_os}, {fraction})")
+    out = np.zeros(n, np.float32)
+    _chk(min(0, lib().dnrp_tx_window(int(N_b_DFT_os), float(fraction), C.c_void_p(out.ctypes.data), n)), "dnrp_tx_window")
+    return out
 
 
 def query_table(name, *args):
@@ -415,6 +429,11 @@ class Phy:
     def set_rx_mode(self, flags):
         """dnrp_ctx_set_rx_mode: RX_MODE_SM_MMSE enables the MMSE receiver for spatial multiplexing."""
         _chk(lib().dnrp_ctx_set_rx_mode(self._ctx, int(flags)), "dnrp_ctx_set_rx_mode")
+
+    def set_tx_windowing(self, fraction):
+        """dnrp_ctx_set_tx_windowing: raised-cosine symbol transitions (the reference's build option
+        PHY_TX_OFDM_WINDOWING) for every later tx_batch; 0 turns them off (the default)."""
+        _chk(lib().dnrp_ctx_set_tx_windowing(self._ctx, float(fraction)), "dnrp_ctx_set_tx_windowing")
 
     def add_network_id(self, nid):
         _chk(lib().dnrp_add_network_id(self._ctx, nid), "dnrp_add_network_id")

@@ -191,6 +191,30 @@ int dnrp_tx_batch(dnrp_ctx* ctx, const dnrp_psdef* psdef, uint32_t n, const dnrp
                   uint32_t S, void* stream);
 
 /*
+ * TX OFDM windowing <- the build option PHY_TX_OFDM_WINDOWING (lib/include/dectnrp/phy/tx/tx.hpp:38,
+ * lib/src/phy/tx/tx.cpp:66-79,126-132,881-908, lib/src/phy/dft/windowing.cpp:34-56): per antenna
+ * stream at the DECT rate, ahead of the resampler, the first N samples of every data-field symbol's
+ * cyclic prefix are multiplied by a rising raised-cosine edge and the cyclic continuation of the
+ * symbol before it (the first N samples of that symbol's body, the STF's taken ahead of its cover
+ * sequence as in tx.cpp:226-234) is added, multiplied by the mirrored edge. The STF's own prefix and
+ * the sample counts do not change. N = roundf(N_b_DFT_os / 8 * fraction) for the STF too.
+ *   fraction  0 (default): off, exactly the transmitter without the option; (0, 1]: on for every later
+ *             dnrp_tx_batch of the context (no context rebuild). DNRP_EINVAL for a NULL context, a
+ *             negative, > 1 or non-finite value.
+ * With windowing on, dnrp_tx_batch returns DNRP_EINVAL for a packet whose N would be below 2 (the
+ * reference asserts it, windowing.cpp:39), before any work is queued.
+ */
+int dnrp_ctx_set_tx_windowing(dnrp_ctx* ctx, float fraction);
+
+/*
+ * Host only: the rising edge rc[n] = cos((n - N) / N * pi / 2)^2, n = 0..N-1, in float
+ * (lib/src/phy/filter/raised_cosine.cpp:30-56) of an N_b_DFT_os-point symbol at `fraction` -- the
+ * table the device uses; the falling edge is rc[N - 1 - n]. Returns N; rising may be NULL to ask for
+ * the length. DNRP_EINVAL for N_b_DFT_os % 8 != 0, a fraction outside (0, 1], N < 2 or cap < N.
+ */
+int dnrp_tx_window(uint32_t N_b_DFT_os, float fraction, float* rising, uint32_t cap);
+
+/*
  * Synchronisation: sync_chunk_t::search() on n windows, each window one chunk whose sync resampler
  * starts with zero history at sample 0 (reset_localbuffer, sync_chunk.cpp:300-311). Detection,
  * coarse peak and fine peak as in the reference; up to max_reports packets per window in search
