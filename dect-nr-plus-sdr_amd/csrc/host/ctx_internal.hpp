@@ -263,6 +263,11 @@ struct sync_tables {  // per (u, b) of the searched STF: sync_chunk_t / crosscor
     geo::resampler_t rs;  // sync resampler (RX direction)
     uint32_t m_star = 0, p_star = 0, npp = 0;
     dbuf taps, taps_pp, tmpl_f, tw_fft;
+    // beta search (dnrp_ctx_set_sync_beta_search), built at its first use for this (u, b): template
+    // spectra [b_idx][n_templates][n_fft] of every b <= this b, plan and twiddles of the 64 bos-point transform
+    bool beta_ready = false;
+    dbuf tmpl_fb, tw_beta;
+    dev::fft_plan beta_plan{};
 };
 
 // tables.cpp: the tables of a configuration, built and uploaded at its first use (nullptr: *err set)
@@ -323,6 +328,11 @@ struct dnrp_ctx {
     // synchronisation: per (u, b) tables, step sums and reports
     std::map<std::pair<uint32_t, uint32_t>, std::unique_ptr<dnrp::host::sync_tables>> synct;
     dbuf sy_P, sy_C, sy_res, sy_cnt, sy_spec, sy_post, sy_state, sy_pk;
+    // beta search at the coarse peak (dnrp_ctx_set_sync_beta_search): off, or the sideband threshold of
+    // later sync calls in dB; sy_band: [n * max_reports][8][6] band powers per antenna (sync_beta_kernel)
+    uint32_t sync_beta_on = 0;
+    float sync_beta_db = -10.0f;
+    dbuf sy_band;
     // ring-buffer gather / continuous-stream synchronisation (stream.cpp)
     dbuf ring_start, ring_win;
     pinned st_ring, st_stream;

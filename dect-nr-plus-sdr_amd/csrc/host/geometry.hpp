@@ -193,4 +193,9 @@ bool rx_twin_plan_ok(const maps_t& m, const rx_plan_t& plain, const rx_plan_t& t
 std::vector<uint32_t> sync_tranches(uint32_t n_steps, uint32_t step, uint32_t stf_len, uint32_t n, uint32_t n_ant,
                                     const std::vector<uint64_t>* forced = nullptr);
 
+// the time-domain STF template of a b packet searched in a (u, b_max, os_min, L, M) stream (host/sync.cpp,
+// stf_template.cpp:93-199): stf_len * L / M hw samples, N_eff_TX in {1, 2, 4, 8}, b <= b_max of b_idx2b
+std::vector<std::complex<double>> sync_template(uint32_t u, uint32_t b_max, uint32_t os_min, uint32_t L, uint32_t M, uint32_t b,
+                                                uint32_t N_eff_TX);
+
 }  // namespace dnrp::geo

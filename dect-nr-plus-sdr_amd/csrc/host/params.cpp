@@ -221,6 +221,17 @@ int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, floa
             host::read_sync(sw);
             for (const uint32_t f : geo::sync_tranches(a(0), a(1), a(2), a(3), a(4), sw.sync_tranche_set ? &sw.sync_tranche : nullptr))
                 v.push_back(static_cast<float>(f));
+        } else if (n == "sync_template") {  // (u, b_max, os_min, L, M, b, N_eff_TX): the fine search's time-domain
+            // STF template of a b packet in a b_max stream, tmpl_len hw samples re/im (stf_template.cpp:93-199)
+            auto listed = [](uint32_t b) { return b == 1 || b == 2 || b == 4 || b == 8 || b == 12 || b == 16; };
+            if (n_arg != 7 || !(a(0) == 1 || a(0) == 2 || a(0) == 4 || a(0) == 8) || !listed(a(1)) || !listed(a(5)) ||
+                a(5) > a(1) || !(a(2) == 1 || a(2) == 2 || a(2) == 4 || a(2) == 8) || a(3) == 0 || a(4) == 0 || a(3) > 64 || a(4) > 64 ||
+                !(a(6) == 1 || a(6) == 2 || a(6) == 4 || a(6) == 8))
+                return DNRP_EINVAL;
+            for (const auto& c : geo::sync_template(a(0), a(1), a(2), a(3), a(4), a(5), a(6))) {
+                v.push_back(static_cast<float>(c.real()));
+                v.push_back(static_cast<float>(c.imag()));
+            }
         } else if (n == "stf_cover_sequence") {
             v.assign(prm::STF_COVER, prm::STF_COVER + 9);
         } else if (n == "symbol_cells") {  // (b, N_TS, N_eff_TX, N_DF): per symbol l = 0..N_DF: PCC, PDC, DRS cells

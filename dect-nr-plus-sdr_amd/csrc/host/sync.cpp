@@ -61,12 +61,14 @@ void fft_host(std::vector<cd>& x, int sign) {  // iterative radix-2 for powers o
     }
 }
 
-// stf_template_t::generate_stf_time_domain (stf_template.cpp:81-206): the STF of (b, N_eff_TX) at
-// N_b_DFT_os = 64 b os, IFFT + CP, 1/sqrt(N_b_OCC/4), cover sequence, TX resampler L/M with the
-// final flush, truncated to stf_len * L / M hw samples
-std::vector<cd> stf_template(uint32_t u, uint32_t b, uint32_t os, const geo::resampler_t& rs_tx, uint32_t N_eff_TX) {
-    const uint32_t N = 56 * b, Nb = 64 * b, Nd = Nb * os;
-    const uint32_t off_lower = Nb / 2 + (Nd - Nb) + 4 * b;  // insert offset + mirror (tx_rx.cpp:197-240)
+// stf_template_t::generate_stf_time_domain (stf_template.cpp:81-206): the STF of (b, N_eff_TX) at the
+// class rate N_b_DFT_os = 64 b_max os for every b <= b_max (insert offset (N_b_DFT_os - 64 b) / 2 +
+// guards_bottom(b) before the mirror), IFFT + CP, 1/sqrt(N_b_OCC(b)/4), cover sequence over patterns
+// of 16 b_max os samples, TX resampler L/M with the final flush, truncated to stf_len * L / M hw samples
+std::vector<cd> stf_template(uint32_t u, uint32_t b_max, uint32_t os, const geo::resampler_t& rs_tx, uint32_t b,
+                             uint32_t N_eff_TX) {
+    const uint32_t N = 56 * b, Nd = 64 * b_max * os;
+    const uint32_t off_lower = Nd - N / 2;  // insert offset + mirror (tx_rx.cpp:197-240)
     const uint32_t cp = (Nd / 4) * (u == 1 ? 3 : 5), len = cp + Nd;
     const auto stf = geo::stf_values(b, N_eff_TX);
     const double scale = 1.0 / std::sqrt(static_cast<double>(static_cast<float>(N / 4)));
@@ -74,7 +76,7 @@ std::vector<cd> stf_template(uint32_t u, uint32_t b, uint32_t os, const geo::res
     for (uint32_t k = 0; k <= N; ++k)
         bins[(k >= N / 2) ? (k - N / 2) : (off_lower + k)] = cd(stf[k].real(), stf[k].imag()) * scale;
     fft_host(bins, +1);  // FFTW backward = unnormalised inverse
-    const uint32_t pat = 16 * b * os, n_pat = u == 1 ? 7 : 9;
+    const uint32_t pat = 16 * b_max * os, n_pat = u == 1 ? 7 : 9;
     std::vector<cd> x(len);
     for (uint32_t i = 0; i < len; ++i) {
         x[i] = bins[(i + Nd - (cp % Nd)) % Nd];
@@ -99,6 +101,41 @@ std::vector<cd> stf_template(uint32_t u, uint32_t b, uint32_t os, const geo::res
         y[m] = acc;
     }
     return y;
+}
+
+// one row of sync_args::tmpl_f: conj(DFT(template)) / n_fft of the (b, N_eff_TX) template in a b_max stream
+void template_spectrum(uint32_t u, uint32_t b_max, uint32_t os, const geo::resampler_t& rs_tx, uint32_t b, uint32_t N_eff_TX,
+                       uint32_t nf, float2* out) {
+    auto tm = stf_template(u, b_max, os, rs_tx, b, N_eff_TX);
+    tm.resize(nf, cd(0, 0));
+    fft_host(tm, -1);
+    for (uint32_t i = 0; i < nf; ++i) {
+        const cd v = std::conj(tm[i]) / static_cast<double>(nf);
+        out[i] = make_float2(static_cast<float>(v.real()), static_cast<float>(v.imag()));
+    }
+}
+
+// b_idx2b (physical_resources.hpp): the packet bandwidths, ascending
+constexpr uint32_t B_IDX2B[6] = {1, 2, 4, 8, 12, 16};
+
+// beta search (dnrp_ctx_set_sync_beta_search), first use for this (u, b_max): the template spectra of
+// every b <= b_max (stf_template.cpp:137-199; row block b_idx, the last one equal to tmpl_f) and the
+// plan and twiddles of the N_b_DFT_os-point transform at the coarse peak (coarse_peak_f_domain.cpp:55)
+bool ensure_beta(const dnrp_cfg& c, sync_tables* t) {
+    if (t->beta_ready) return true;
+    const uint32_t nf = 1u << t->log2_fft;
+    const auto rs_tx = geo::make_resampler(c.L, c.M, c.os_min, prm::RS_TX);
+    uint32_t nb = 0;
+    while (nb < 6 && B_IDX2B[nb] <= t->b) ++nb;
+    std::vector<float2> tf(size_t(nb) * t->n_templates * nf);
+    for (uint32_t bi = 0; bi < nb; ++bi)
+        for (uint32_t k = 0; k < t->n_templates; ++k)
+            template_spectrum(t->u, t->b, c.os_min, rs_tx, B_IDX2B[bi], 1u << k, nf, &tf[(size_t(bi) * t->n_templates + k) * nf]);
+    const uint32_t N = prm::N_SAMPLES_STF_PATTERN * 4 * t->bos;  // 64 b_max os
+    t->beta_plan = make_plan(N);
+    if (!t->tmpl_fb.upload(tf) || !t->tw_beta.upload(twiddles(N))) return false;
+    t->beta_ready = true;
+    return true;
 }
 
 sync_tables* get_sync(dnrp_ctx* ctx, uint32_t u, uint32_t b, int* err) {
@@ -133,15 +170,7 @@ sync_tables* get_sync(dnrp_ctx* ctx, uint32_t u, uint32_t b, int* err) {
     }
     const auto rs_tx = geo::make_resampler(c.L, c.M, c.os_min, prm::RS_TX);  // stf_template.cpp: TX filter
     std::vector<float2> tf(size_t(t->n_templates) * nf);
-    for (uint32_t k = 0; k < t->n_templates; ++k) {
-        auto tm = stf_template(u, b, c.os_min, rs_tx, 1u << k);
-        tm.resize(nf, cd(0, 0));
-        fft_host(tm, -1);
-        for (uint32_t i = 0; i < nf; ++i) {
-            const cd v = std::conj(tm[i]) / static_cast<double>(nf);
-            tf[size_t(k) * nf + i] = make_float2(static_cast<float>(v.real()), static_cast<float>(v.imag()));
-        }
-    }
+    for (uint32_t k = 0; k < t->n_templates; ++k) template_spectrum(u, b, c.os_min, rs_tx, b, 1u << k, nf, &tf[size_t(k) * nf]);
     std::vector<float> pp = (c.L == 1 && c.M == 1) ? std::vector<float>{0.f} : taps_polyphase(t->rs, &t->npp);
     if (c.L == 1 && c.M == 1) t->npp = 0;
     if (!t->taps.upload(t->rs.h) || !t->taps_pp.upload(pp) || !t->tmpl_f.upload(tf) || !t->tw_fft.upload(twiddles(nf))) {
@@ -152,7 +181,33 @@ sync_tables* get_sync(dnrp_ctx* ctx, uint32_t u, uint32_t b, int* err) {
     return slot.get();
 }
 
+// common::adt::db2mag of the threshold: the reference compares a power ratio against this magnitude
+// conversion (coarse_peak_f_domain.cpp:143-144,177); kept as it is there
+float beta_linear(float db) { return std::pow(10.0f, db / 20.0f); }
+
 }  // namespace
+
+extern "C" int dnrp_ctx_set_sync_beta_search(dnrp_ctx* ctx, uint32_t on, float threshold_db) {
+    if (!ctx || on > 1 || !std::isfinite(threshold_db)) return DNRP_EINVAL;
+    ctx->sync_beta_on = on;
+    ctx->sync_beta_db = threshold_db;
+    return DNRP_OK;
+}
+
+extern "C" int dnrp_ctx_get_sync_beta_search(const dnrp_ctx* ctx, uint32_t* on, float* threshold_db, float* threshold_linear) {
+    if (!ctx) return DNRP_EINVAL;
+    if (on) *on = ctx->sync_beta_on;
+    if (threshold_db) *threshold_db = ctx->sync_beta_db;
+    if (threshold_linear) *threshold_linear = beta_linear(ctx->sync_beta_db);
+    return DNRP_OK;
+}
+
+// dnrp_query_table "sync_template": the time-domain STF template of a b packet in a (u, b_max, os_min,
+// L, M) stream, tmpl_len hw samples (the row get_sync / ensure_beta transform for sync_fine_kernel)
+std::vector<std::complex<double>> dnrp::geo::sync_template(uint32_t u, uint32_t b_max, uint32_t os_min, uint32_t L, uint32_t M,
+                                                           uint32_t b, uint32_t N_eff_TX) {
+    return stf_template(u, b_max, os_min, geo::make_resampler(L, M, os_min, prm::RS_TX), b, N_eff_TX);
+}
 
 // Tranche schedule of one call: the frontiers (exclusive step ends, ascending, the last n_steps) at
 // which the detection runs on the step sums computed so far. sync_chunk_t::search() resamples and
@@ -248,6 +303,15 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
     a.tw_fft = t->tw_fft.as<float2>();
     a.u = sc->u;
     a.b = sc->b;
+    if (ctx->sync_beta_on && sc->b > 1) {  // b_max == 1: nothing to estimate (coarse_peak_f_domain.cpp:97-99)
+        if (!ensure_beta(c, t) ||
+            !ctx->sy_band.ensure(size_t(n) * sc->max_reports * 8 * dev::SYNC_BANDS * sizeof(float)))
+            return DNRP_ENOMEM;
+        a.beta_on = 1;
+        a.beta_thr = beta_linear(ctx->sync_beta_db);
+        a.band = ctx->sy_band.as<float>();
+        a.tmpl_f = t->tmpl_fb.as<float2>();
+    }
     a.det_stage = dev::sync_detect_stage(a);
     if (dev::sync_detect_lds(a) > 160 * 1024 || (16 + 2 * (size_t(1) << a.log2_fft)) * sizeof(float2) > 160 * 1024)
         return DNRP_EUNSUPPORTED;
@@ -357,6 +421,16 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
     ctx->tic("sync_post", st);
     if (dev::launch_sync_post(a, n, st) != hipSuccess) return DNRP_EDEVICE;
     ctx->toc("sync_post", st);
+    if (a.beta_on) {  // the band powers sync_fine decides b from; off: no launch, no report field written
+        dev::sync_beta_args ba{};
+        ba.plan = t->beta_plan;
+        ba.tw = t->tw_beta.as<float2>();
+        ba.band = ctx->sy_band.as<float>();
+        ba.cp = a.stf_len - ba.plan.N;
+        ctx->tic("sync_beta", st);
+        if (dev::launch_sync_beta(a, ba, n, st) != hipSuccess) return DNRP_EDEVICE;
+        ctx->toc("sync_beta", st);
+    }
     ctx->tic("sync_fine", st);
     if (dev::launch_sync_fine(a, n, st) != hipSuccess) return DNRP_EDEVICE;
     ctx->toc("sync_fine", st);

@@ -454,6 +454,19 @@ struct sync_args {
     uint32_t rounds;                           // split rounds per tranche = detections per window searched by sync_peak_kernel
     uint32_t skip;                             // 1 (every tranche but a call's first): step-sum waves of finished
                                                // windows (state[w].pend == 2) return at once
+    // beta search at the coarse peak (coarse_peak_f_domain.cpp:70-193). beta_on 0: r.b = b and tmpl_f is the
+    // one row block of b. 1: sync_fine_kernel decides r.b from sync_beta_kernel's band powers and takes the
+    // row block b_idx(r.b) of tmpl_f [b_idx][n_templates][n_fft]
+    uint32_t beta_on;
+    float beta_thr;                            // linear threshold on the sideband / centre power ratio
+    const float* band;                         // [n * max_reports][8][SYNC_BANDS] band powers per antenna
+};
+constexpr uint32_t SYNC_BANDS = 6;  // b_idx2b = {1, 2, 4, 8, 12, 16}: band i = the 32-bin half-bands [b(i-1), b(i)) on either side
+struct sync_beta_args {  // sync_beta_kernel: the N = 64 bos-point transform of the STF's last N samples
+    fft_plan plan;
+    const float2* tw;  // forward twiddles of N
+    float* band;       // sync_args::band
+    uint32_t cp;       // N_samples_STF_CP_only_os: 3/4 N (u = 1) or 5/4 N
 };
 struct sync_state {  // sync_detect_kernel's loop registers (autocorrelator_detection / _peak state)
     uint32_t s_cur, ignore, nrep, pend;  // pend: 0 searching, 1 coarse peak pending, 2 finished
@@ -473,6 +486,7 @@ hipError_t launch_sync_peak(const sync_args& a, uint32_t n, hipStream_t st);
 bool sync_peak_ok(const sync_args& a);
 bool sync_taps_match(const float* h, size_t n);  // compiled-in 9/10 sync taps == run-time taps
 hipError_t launch_sync_post(const sync_args& a, uint32_t n, hipStream_t st);
+hipError_t launch_sync_beta(const sync_args& a, const sync_beta_args& ba, uint32_t n, hipStream_t st);
 hipError_t launch_sync_fine(const sync_args& a, uint32_t n, hipStream_t st);
 uint32_t sync_detect_stage(const sync_args& a);
 size_t sync_detect_lds(const sync_args& a);

@@ -1487,6 +1487,70 @@ __global__ void __launch_bounds__(SYNC_THREADS) __attribute__((amdgpu_waves_per_
     }
 }
 
+// ===================================================================== beta at the coarse peak
+// coarse_peak_f_domain_t::process (coarse_peak_f_domain.cpp:70-92) for one (report, antenna), launched
+// only with the beta search on: the last N = 64 bos samples of the STF at the coarse peak (the samples
+// sync_post_kernel resamples, from N_samples_STF_CP_only_os on; no CFO correction, as the reference),
+// their N-point transform in LDS, and after the FFT shift the power of every band the decision can ask
+// for: band i = the 32-bin half-bands [b_idx2b[i - 1], b_idx2b[i]) left and right of the centre. Every
+// searched antenna, with or without a valid coarse peak (estimate_beta sums all nof_antennas_limited).
+// Only the band powers leave; sync_fine_kernel sums them in antenna order and decides.
+template <int LR, int MR, int HLR, bool CT>
+__global__ void __launch_bounds__(SYNC_THREADS) sync_beta_kernel(sync_args A, sync_beta_args B) {
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    double* red = reinterpret_cast<double*>(smem);  // [24]
+    const uint32_t N = B.plan.N;
+    float2* xb = smem + 12;
+    float2* yb = xb + N;
+    const uint32_t rep = blockIdx.x / A.n_ant, a = blockIdx.x % A.n_ant, w = rep / A.max_reports;
+    const sync_res* rp = A.res + rep;
+    if (!rp->found) return;  // uniform: the whole workgroup leaves
+    const float2* x = A.iq + w * A.win_stride + a * A.ant_stride;
+    resample_direct<LR, MR, HLR, CT>(A, x, static_cast<int64_t>(rp->coarse_local) + B.cp, N, [&](uint32_t i, float2 v) { xb[i] = v; });
+    __syncthreads();
+    const float2* S = fft_any<-1>(xb, yb, B.tw, B.plan);
+    // FFT shift: bin k sits d = k bins right of the centre (k < N / 2) or N - 1 - k bins left of it
+    double p[SYNC_BANDS] = {};
+    for (uint32_t k = threadIdx.x; k < N; k += blockDim.x) {
+        const uint32_t h = (k < N / 2 ? k : N - 1 - k) >> 5;  // 32-bin half-band, 0 at the centre
+        const uint32_t band = h < 1 ? 0u : h < 2 ? 1u : h < 4 ? 2u : h < 8 ? 3u : h < 12 ? 4u : h < 16 ? 5u : SYNC_BANDS;
+        const double v = static_cast<double>(cnorm(S[k]));
+#pragma unroll
+        for (uint32_t i = 0; i < SYNC_BANDS; ++i) p[i] += band == i ? v : 0.0;
+    }
+    block_sum3(p[0], p[1], p[2], red);
+    block_sum3(p[3], p[4], p[5], red);
+    if (threadIdx.x == 0) {
+        float* o = B.band + (size_t(rep) * 8 + a) * SYNC_BANDS;
+#pragma unroll
+        for (uint32_t i = 0; i < SYNC_BANDS; ++i) o[i] = static_cast<float>(p[i]);
+    }
+}
+
+// estimate_beta (coarse_peak_f_domain.cpp:94-193) on the band powers of one report, summed over the
+// searched antennas in antenna order: from b = 1 the next b of b_idx2b is taken while the sideband's
+// power per bin over the centre band's exceeds the threshold. The loop ends at b_max (the reference's
+// runs one step further into its asserts).
+__device__ uint32_t sync_beta_decide(const sync_args& A, const float* band) {
+    const uint32_t b_idx2b[SYNC_BANDS] = {1, 2, 4, 8, 12, 16};
+    float pw[SYNC_BANDS];
+    for (uint32_t i = 0; i < SYNC_BANDS; ++i) {
+        pw[i] = 0.f;
+        for (uint32_t a = 0; a < A.n_ant; ++a) pw[i] += band[a * SYNC_BANDS + i];
+    }
+    uint32_t b_est = 1;
+    float centre = pw[0];
+    for (uint32_t i = 1; i < SYNC_BANDS && b_est < A.b; ++i) {
+        const uint32_t n_side = (b_idx2b[i] - b_est) * 32;
+        const float centre_norm = centre / static_cast<float>(b_est * 64);
+        const float side_norm = pw[i] / static_cast<float>(n_side * 2);
+        if (!(side_norm / centre_norm > A.beta_thr)) break;
+        b_est = b_idx2b[i];
+        centre += pw[i];
+    }
+    return b_est;
+}
+
 // ===================================================================== fine peak
 constexpr uint32_t SYNC_FINE_THREADS = 512;  // 8 waves: the FFT passes' butterflies 2 per thread
 #ifndef DNRP_FINE_WPE
@@ -1522,6 +1586,15 @@ __global__ void __launch_bounds__(SYNC_FINE_THREADS) __attribute__((amdgpu_waves
         __syncthreads();
     }
     const uint32_t nf = 1u << A.log2_fft;
+    // beta search on (kernel argument, uniform): the packet's b from sync_beta_kernel's band powers, every
+    // thread the same sums in the same order; the templates below are the row block of that b
+    const float2* tmpl = A.tmpl_f;
+    if (A.beta_on) {
+        const uint32_t b_est = sync_beta_decide(A, A.band + size_t(blockIdx.x) * 8 * SYNC_BANDS);
+        const uint32_t b_idx = b_est <= 2 ? b_est - 1 : b_est / 4 + 1;  // b2b_idx: 1 2 4 8 12 16 -> 0..5
+        tmpl += static_cast<size_t>(b_idx) * A.n_templates * nf;
+        if (threadIdx.x == 0) rp->b = b_est;
+    }
     // power-of-4 sizes (4096 for C3 / C4): in-place radix-4 DIT on one LDS buffer, the inputs stored
     // at their base-4 digit-reversed positions (ip); otherwise the two-buffer Stockham passes
     const bool ip = (A.log2_fft & 1u) == 0;
@@ -1579,7 +1652,7 @@ __global__ void __launch_bounds__(SYNC_FINE_THREADS) __attribute__((amdgpu_waves
     // per template: its peak metric and index in the header's upper half (s_val / s_idx 8 + k; the
     // wave maxima use 0..7), written by thread 0, the only reader: no registers held across the FFTs
     for (uint32_t k = 0; k < A.n_templates; ++k) {
-        const float2* T = A.tmpl_f + static_cast<size_t>(k) * nf;
+        const float2* T = tmpl + static_cast<size_t>(k) * nf;
         if constexpr (DNRP_FINE_BATCH > 1) {
             // the spectrum row and the template read DNRP_FINE_BATCH per thread at a time (one L2
             // round trip per batch instead of one per element), then the products stored
@@ -1862,6 +1935,23 @@ hipError_t launch_sync_post(const sync_args& a, uint32_t n, hipStream_t st) {
         hipLaunchKernelGGL((sync_post_kernel<1, 1, 0, false>), g, dim3(SYNC_THREADS), lds, st, a);
     else
         hipLaunchKernelGGL((sync_post_kernel<0, 0, 0, false>), g, dim3(SYNC_THREADS), lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_sync_beta(const sync_args& a, const sync_beta_args& ba, uint32_t n, hipStream_t st) {
+    const dim3 g(n * a.max_reports * a.n_ant);
+    const size_t lds = (12 + 2 * size_t(ba.plan.N)) * sizeof(float2);
+    if (lds > 160 * 1024 || ba.cp + ba.plan.N != a.stf_len) return hipErrorInvalidValue;
+    if (a.L == 9 && a.M == 10 && a.hl == 24 && a.ct_taps)  // compiled-in 9/10 taps, as sync_post_kernel
+        hipLaunchKernelGGL((sync_beta_kernel<9, 10, 24, true>), g, dim3(SYNC_THREADS), lds, st, a, ba);
+    else if (a.L == 9 && a.M == 10 && a.hl == 24)
+        hipLaunchKernelGGL((sync_beta_kernel<9, 10, 24, false>), g, dim3(SYNC_THREADS), lds, st, a, ba);
+    else if (a.L == 9 && a.M == 10 && a.hl == 4)
+        hipLaunchKernelGGL((sync_beta_kernel<9, 10, 4, false>), g, dim3(SYNC_THREADS), lds, st, a, ba);
+    else if (a.L == 1 && a.M == 1)
+        hipLaunchKernelGGL((sync_beta_kernel<1, 1, 0, false>), g, dim3(SYNC_THREADS), lds, st, a, ba);
+    else
+        hipLaunchKernelGGL((sync_beta_kernel<0, 0, 0, false>), g, dim3(SYNC_THREADS), lds, st, a, ba);
     return hipGetLastError();
 }
 

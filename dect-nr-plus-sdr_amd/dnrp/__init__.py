@@ -196,7 +196,7 @@ EXPORTS = ["dnrp_ctx_create", "dnrp_ctx_destroy", "dnrp_add_network_id", "dnrp_g
            "dnrp_harq_rx_destroy", "dnrp_pdc_decode_batch", "dnrp_pdc_encode_batch",
            "dnrp_pcc_decode_batch", "dnrp_pdc_decode_batch_harq", "dnrp_pdc_softbuffer_size",
            "dnrp_pcc_encode_batch", "dnrp_query_table", "dnrp_ctx_set_rx_mode", "dnrp_ctx_set_tx_windowing",
-           "dnrp_tx_window"]
+           "dnrp_tx_window", "dnrp_ctx_set_sync_beta_search", "dnrp_ctx_get_sync_beta_search"]
 
 _lib = None
 
@@ -225,6 +225,8 @@ def lib():
         L.dnrp_ctx_set_rx_mode.argtypes = [P, C.c_uint32]
         L.dnrp_ctx_set_tx_windowing.argtypes = [P, C.c_float]
         L.dnrp_tx_window.argtypes = [C.c_uint32, C.c_float, P, C.c_uint32]
+        L.dnrp_ctx_set_sync_beta_search.argtypes = [P, C.c_uint32, C.c_float]
+        L.dnrp_ctx_get_sync_beta_search.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.dnrp_ring_gather.argtypes = [P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, P, C.c_uint32, P, P]
         L.dnrp_channel_batch.argtypes = [P, C.POINTER(ChannelCfg), C.c_uint32, C.c_uint32, P, C.c_uint32, C.c_uint32, P, P,
                                          P, C.c_uint32, P]
@@ -434,6 +436,20 @@ class Phy:
         """dnrp_ctx_set_tx_windowing: raised-cosine symbol transitions (the reference's build option
         PHY_TX_OFDM_WINDOWING) for every later tx_batch; 0 turns them off (the default)."""
         _chk(lib().dnrp_ctx_set_tx_windowing(self._ctx, float(fraction)), "dnrp_ctx_set_tx_windowing")
+
+    def set_sync_beta_search(self, on, threshold_db=-10.0):
+        """dnrp_ctx_set_sync_beta_search: every later rx_sync_batch / rx_sync_stream estimates the packet's
+        b at the coarse peak (the reference's build option
+        RX_SYNC_PARAM_AUTOCORRELATOR_PEAK_FIND_BETA_THRESHOLD_DB_OR_ASSUME_MAX_OF_RDC) and cross-correlates
+        against the templates of that b; off (the default) reports b = SyncCfg.b."""
+        _chk(lib().dnrp_ctx_set_sync_beta_search(self._ctx, int(on), float(threshold_db)), "dnrp_ctx_set_sync_beta_search")
+
+    def sync_beta_search(self):
+        """dnrp_ctx_get_sync_beta_search: (on, threshold_db, threshold_linear = 10 ** (dB / 20))."""
+        on, db, lin = C.c_uint32(), C.c_float(), C.c_float()
+        _chk(lib().dnrp_ctx_get_sync_beta_search(self._ctx, C.byref(on), C.byref(db), C.byref(lin)),
+             "dnrp_ctx_get_sync_beta_search")
+        return bool(on.value), db.value, lin.value
 
     def add_network_id(self, nid):
         _chk(lib().dnrp_add_network_id(self._ctx, nid), "dnrp_add_network_id")

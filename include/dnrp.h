@@ -227,6 +227,35 @@ int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32_t n, const
                        uint64_t ant_stride, uint32_t S_win, dnrp_sync_result* res, uint32_t* n_found, void* stream);
 
 /*
+ * Beta search at the coarse peak <- the build option
+ * RX_SYNC_PARAM_AUTOCORRELATOR_PEAK_FIND_BETA_THRESHOLD_DB_OR_ASSUME_MAX_OF_RDC
+ * (lib/include/dectnrp/phy/rx/sync/sync_param.hpp:238-244, off by default there too). A receiver of a class
+ * with b_max is triggered by packets of every b <= b_max; with the search on, the synchronisation finds
+ * the packet's b and cross-correlates against the STF templates of that b:
+ *  - coarse_peak_f_domain_t::process / estimate_beta (lib/src/phy/rx/sync/coarse_peak_f_domain.cpp:70-193):
+ *    for every searched antenna the N = 64 b_max os_min DECT-rate samples starting
+ *    N_samples_STF_CP_only_os after coarse_peak_time_local are transformed (no CFO correction), and after
+ *    the FFT shift, from b = 1 (bins [N/2 - 32, N/2 + 32)), the next b' of b_idx2b = {1, 2, 4, 8, 12, 16}
+ *    is taken while (side / (2 n_side)) / (centre / (64 b)) > threshold_linear, the sideband being the
+ *    n_side = (b' - b) 32 bins on either side of the current band, powers summed over the antennas;
+ *  - stf_template_t (lib/src/phy/rx/sync/stf_template.cpp:137-199): templates of every b <= b_max at the
+ *    class rate; the fine search takes the rows of the report's b (crosscorrelator.cpp:159).
+ * dnrp_sync_cfg::b stays the class maximum whose sample rate the stream has; the candidates are the
+ * values of b_idx2b <= it, and the search ends there (the reference's loop would test one b further and
+ * stops in its asserts). cfo_integer_rad stays 0 (the reference's integer-CFO search is an #error).
+ *   on            0 (default): exactly the synchronisation without the option, b = dnrp_sync_cfg::b, the
+ *                 same templates, no further launch. 1: on for every later dnrp_rx_sync_batch and
+ *                 dnrp_rx_sync_stream of the context (no context rebuild); the templates of the other b
+ *                 are built at the first such call per (u, b).
+ *   threshold_db  the reference's value is -10. threshold_linear = 10^(dB / 20): the reference converts
+ *                 with db2mag and compares a power ratio against it (coarse_peak_f_domain.cpp:143-144,177);
+ *                 mirrored, not repaired.
+ * DNRP_EINVAL for a NULL context, on > 1 or a non-finite threshold_db. The getter's outputs may be NULL.
+ */
+int dnrp_ctx_set_sync_beta_search(dnrp_ctx* ctx, uint32_t on, float threshold_db);
+int dnrp_ctx_get_sync_beta_search(const dnrp_ctx* ctx, uint32_t* on, float* threshold_db, float* threshold_linear);
+
+/*
  * RX phase 1: synchronised PCC demodulation of n packets. Each packet is processed with the
  * (u, b, N_eff_TX) of its own sync report (packets are grouped internally, like independent
  * demoddecod_rx_pcc calls).
@@ -493,7 +522,12 @@ const char* dnrp_param_name(uint32_t index);
  *                                indices k of each transmit stream ts_first..ts_last (drs.cpp:73-125)
  *   "rx_epoch_syms" (b, N_TS, N_eff_TX, N_DF, mode_lr, stride)   the epoch receiver's symbol ownership of
  *                                the PDC phase: ok (0 / 1), per plan epoch its symbol count and symbols,
- *                                then the DRS-pass symbols */
+ *                                then the DRS-pass symbols
+ *   "sync_template" (u, b_max, os_min, L, M, b, N_eff_TX)   the fine search's time-domain STF template of a b
+ *                                packet in the stream of a (u, b_max, os_min, L, M) receiver: tmpl_len =
+ *                                stf_len L / M hw samples re/im (stf_template.cpp:93-199; the row of b = b_max
+ *                                is the one searched without dnrp_ctx_set_sync_beta_search). DNRP_EINVAL for
+ *                                b > b_max, a b outside {1, 2, 4, 8, 12, 16} or an N_eff_TX outside {1, 2, 4, 8} */
 int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, float* out, uint32_t cap);
 
 /* Kernel timing (only when the environment has DNRP_TIMING=1 at dnrp_ctx_create): HIP events
