@@ -333,6 +333,12 @@ struct dnrp_ctx {
     uint32_t sync_beta_on = 0;
     float sync_beta_db = -10.0f;
     dbuf sy_band;
+    // fine search over every antenna with a coarse peak (dnrp_ctx_set_sync_fine_all_antennas): the setting
+    // of later sync calls; sy_fine_m / sy_fine_i: the per-antenna table [n * max_reports][8][4] of the latest
+    // dnrp_rx_sync_batch that ran with it on, sync_fine_reports its n * max_reports (0: none, or it ran off)
+    uint32_t sync_fine_all = 0;
+    uint32_t sync_fine_reports = 0;
+    dbuf sy_fine_m, sy_fine_i;
     // ring-buffer gather / continuous-stream synchronisation (stream.cpp)
     dbuf ring_start, ring_win;
     pinned st_ring, st_stream;

@@ -202,6 +202,29 @@ extern "C" int dnrp_ctx_get_sync_beta_search(const dnrp_ctx* ctx, uint32_t* on, 
     return DNRP_OK;
 }
 
+extern "C" int dnrp_ctx_set_sync_fine_all_antennas(dnrp_ctx* ctx, uint32_t on) {
+    if (!ctx || on > 1) return DNRP_EINVAL;
+    ctx->sync_fine_all = on;
+    return DNRP_OK;
+}
+
+extern "C" int dnrp_ctx_get_sync_fine_all_antennas(const dnrp_ctx* ctx, uint32_t* on) {
+    if (!ctx) return DNRP_EINVAL;
+    if (on) *on = ctx->sync_fine_all;
+    return DNRP_OK;
+}
+
+extern "C" int dnrp_rx_sync_fine_peaks(dnrp_ctx* ctx, uint32_t n_reports, float* metric, uint32_t* index, void* stream) {
+    if (!ctx || !metric || !index) return DNRP_EINVAL;
+    if (ctx->sync_fine_reports == 0) return DNRP_ESTATE;
+    if (n_reports != ctx->sync_fine_reports) return DNRP_EINVAL;
+    (void)hipSetDevice(ctx->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIPCHK(hipMemcpyAsync(metric, ctx->sy_fine_m.p, size_t(n_reports) * 32 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(index, ctx->sy_fine_i.p, size_t(n_reports) * 32 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return DNRP_OK;
+}
+
 // dnrp_query_table "sync_template": the time-domain STF template of a b packet in a (u, b_max, os_min,
 // L, M) stream, tmpl_len hw samples (the row get_sync / ensure_beta transform for sync_fine_kernel)
 std::vector<std::complex<double>> dnrp::geo::sync_template(uint32_t u, uint32_t b_max, uint32_t os_min, uint32_t L, uint32_t M,
@@ -255,6 +278,7 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
         return DNRP_EINVAL;
     if (sc->max_reports == 0 || S_win == 0 || sc->chunk_len < ctx->cfg.L) return DNRP_EINVAL;
     (void)hipSetDevice(ctx->cfg.device);
+    ctx->sync_fine_reports = 0;  // dnrp_rx_sync_fine_peaks: the table of this call, once it has run with the setting on
     int err = DNRP_OK;
     sync_tables* t = get_sync(ctx, sc->u, sc->b, &err);
     if (!t) return err;
@@ -312,16 +336,24 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
         a.band = ctx->sy_band.as<float>();
         a.tmpl_f = t->tmpl_fb.as<float2>();
     }
+    a.fine_all = ctx->sync_fine_all;
     a.det_stage = dev::sync_detect_stage(a);
     if (dev::sync_detect_lds(a) > 160 * 1024 || (16 + 2 * (size_t(1) << a.log2_fft)) * sizeof(float2) > 160 * 1024)
         return DNRP_EUNSUPPORTED;
     const size_t nsa = size_t(n) * a.n_ant * a.n_steps;
     if (!ctx->sy_P.ensure(nsa * sizeof(float)) || !ctx->sy_C.ensure(nsa * sizeof(float2)) ||
         !ctx->sy_res.ensure(size_t(n) * a.max_reports * sizeof(dev::sync_res)) || !ctx->sy_cnt.ensure(size_t(n) * 4) ||
-        !ctx->sy_spec.ensure(size_t(n) * a.max_reports * (size_t(1) << a.log2_fft) * sizeof(float2)) ||
+        !ctx->sy_spec.ensure(size_t(n) * a.max_reports * (a.fine_all ? a.n_ant : 1u) * (size_t(1) << a.log2_fft) * sizeof(float2)) ||
         !ctx->sy_post.ensure(size_t(n) * a.max_reports * 8 * sizeof(float)) ||
         !ctx->sy_state.ensure(size_t(n) * sizeof(dev::sync_state)) || !ctx->sy_pk.ensure(size_t(n) * 8 * sizeof(float2)))
         return DNRP_ENOMEM;
+    if (a.fine_all) {
+        if (!ctx->sy_fine_m.ensure(size_t(n) * a.max_reports * 32 * sizeof(float)) ||
+            !ctx->sy_fine_i.ensure(size_t(n) * a.max_reports * 32 * sizeof(uint32_t)))
+            return DNRP_ENOMEM;
+        a.fine_m = ctx->sy_fine_m.as<float>();
+        a.fine_i = ctx->sy_fine_i.as<uint32_t>();
+    }
     a.state = ctx->sy_state.as<dev::sync_state>();
     a.pk = ctx->sy_pk.as<float2>();
     a.spec = ctx->sy_spec.as<float2>();
@@ -434,6 +466,7 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
     ctx->tic("sync_fine", st);
     if (dev::launch_sync_fine(a, n, st) != hipSuccess) return DNRP_EDEVICE;
     ctx->toc("sync_fine", st);
+    if (a.fine_all) ctx->sync_fine_reports = n * a.max_reports;
     HIPCHK(hipMemcpyAsync(res, a.res, size_t(n) * a.max_reports * sizeof(dev::sync_res), hipMemcpyDeviceToHost, st));
     if (n_found) HIPCHK(hipMemcpyAsync(n_found, a.n_found, size_t(n) * 4, hipMemcpyDeviceToHost, st));
     return DNRP_OK;

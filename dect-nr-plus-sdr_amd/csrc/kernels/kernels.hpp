@@ -460,6 +460,13 @@ struct sync_args {
     uint32_t beta_on;
     float beta_thr;                            // linear threshold on the sideband / centre power ratio
     const float* band;                         // [n * max_reports][8][SYNC_BANDS] band powers per antenna
+    // fine search over every antenna with a coarse peak (crosscorrelator.cpp:137-147, 218-248). fine_all 0:
+    // sync_fine_kernel, one workgroup per report, the strongest antenna. 1: sync_fine_ant_kernel, one
+    // workgroup per (report, antenna) and spec one row per workgroup [n * max_reports * n_ant][n_fft], then
+    // sync_fine_combine_kernel on the table
+    uint32_t fine_all;
+    float* fine_m;                             // [n * max_reports][8][4] peak metric per (antenna, template), 0 where
+    uint32_t* fine_i;                          // not processed; its index relative to the search start
 };
 constexpr uint32_t SYNC_BANDS = 6;  // b_idx2b = {1, 2, 4, 8, 12, 16}: band i = the 32-bin half-bands [b(i-1), b(i)) on either side
 struct sync_beta_args {  // sync_beta_kernel: the N = 64 bos-point transform of the STF's last N samples

@@ -1566,23 +1566,53 @@ constexpr uint32_t SYNC_FINE_THREADS = 512;  // 8 waves: the FFT passes' butterf
 #define DNRP_FINE_BATCH 8  // spectrum x template loads in flight per thread (1: one per loop iteration)
 #endif
 
-__global__ void __launch_bounds__(SYNC_FINE_THREADS) __attribute__((amdgpu_waves_per_eu(DNRP_FINE_WPE))) sync_fine_kernel(sync_args A) {
+// fractional CFO of a report: metric-weighted antenna mean of sync_post_kernel's terms, in antenna order
+__device__ __forceinline__ float sync_cfo_frac(const sync_args& A, const sync_res* rp, uint32_t rep) {
+    float cfo_w = 0.f, msum = 0.f;
+    for (uint32_t a = 0; a < A.n_ant; ++a) {
+        const float m = rp->coarse_metric[a];
+        if (!(m > 0.f)) continue;
+        msum += m;
+        cfo_w += A.post[size_t(rep) * 8 + a];
+    }
+    return cfo_w / msum;
+}
+
+// The fine search of one workgroup (crosscorrelator.cpp:122-249), two forms:
+//  ALL = false  one workgroup per report: the antenna with the largest coarse-peak metric against every
+//               template, N_eff_TX and the fine peak written to the report (the reference without
+//               RX_SYNC_PARAM_CROSSCORRELATOR_ALL_ANTENNAS_OR_ONLY_STRONGEST);
+//  ALL = true   one workgroup per (report, antenna), blockIdx.x = rep * n_ant + a: antenna a against every
+//               template, (metric, index) per template into A.fine_m / A.fine_i [rep][8][4]; workgroups of
+//               reports not found and of antennas without a coarse peak leave after writing zeros, the
+//               last antenna's workgroup also zeroes the rows n_ant..7. The report is only read here (the
+//               CFO and b derived in registers from coarse_metric, post and band, which no workgroup of
+//               this launch writes); sync_fine_combine_kernel writes it afterwards.
+template <bool ALL>
+__device__ __forceinline__ void sync_fine_body(const sync_args& A) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float* s_val = reinterpret_cast<float*>(smem);  // [16]
     uint32_t* s_idx = reinterpret_cast<uint32_t*>(smem + 8);  // [16]
-    sync_res* rp = A.res + blockIdx.x;
-    if (!rp->found) return;
-    const uint32_t w = blockIdx.x / A.max_reports;
-    {  // fractional CFO: metric-weighted antenna mean of sync_post_kernel's terms, in antenna order
-        float cfo_w = 0.f, msum = 0.f;
-        for (uint32_t a = 0; a < A.n_ant; ++a) {
-            const float m = rp->coarse_metric[a];
-            if (!(m > 0.f)) continue;
-            msum += m;
-            cfo_w += A.post[size_t(blockIdx.x) * 8 + a];
+    const uint32_t rep = ALL ? blockIdx.x / A.n_ant : blockIdx.x;
+    sync_res* rp = A.res + rep;
+    uint32_t best = ALL ? blockIdx.x % A.n_ant : 0u;  // the antenna searched
+    float cfo_frac = 0.f;
+    if constexpr (!ALL)
+        if (!rp->found) return;
+    const uint32_t w = rep / A.max_reports;
+    if constexpr (ALL) {
+        const bool live = rp->found && rp->coarse_metric[best] > 0.f;
+        const uint32_t rows = best + 1 == A.n_ant ? 8 - best : 1;  // table rows this workgroup owns
+        if (threadIdx.x < 4 * rows && (!live || threadIdx.x >= 4)) {
+            A.fine_m[(size_t(rep) * 8 + best) * 4 + threadIdx.x] = 0.f;
+            A.fine_i[(size_t(rep) * 8 + best) * 4 + threadIdx.x] = 0u;
         }
+        if (!live) return;  // uniform: the whole workgroup leaves
+        cfo_frac = sync_cfo_frac(A, rp, rep);
+    } else {
+        cfo_frac = sync_cfo_frac(A, rp, rep);
         __syncthreads();  // every thread has read the report before thread 0 updates it
-        if (threadIdx.x == 0) rp->cfo_frac = cfo_w / msum;
+        if (threadIdx.x == 0) rp->cfo_frac = cfo_frac;
         __syncthreads();
     }
     const uint32_t nf = 1u << A.log2_fft;
@@ -1590,10 +1620,11 @@ __global__ void __launch_bounds__(SYNC_FINE_THREADS) __attribute__((amdgpu_waves
     // thread the same sums in the same order; the templates below are the row block of that b
     const float2* tmpl = A.tmpl_f;
     if (A.beta_on) {
-        const uint32_t b_est = sync_beta_decide(A, A.band + size_t(blockIdx.x) * 8 * SYNC_BANDS);
+        const uint32_t b_est = sync_beta_decide(A, A.band + size_t(rep) * 8 * SYNC_BANDS);
         const uint32_t b_idx = b_est <= 2 ? b_est - 1 : b_est / 4 + 1;  // b2b_idx: 1 2 4 8 12 16 -> 0..5
         tmpl += static_cast<size_t>(b_idx) * A.n_templates * nf;
-        if (threadIdx.x == 0) rp->b = b_est;
+        if constexpr (!ALL)
+            if (threadIdx.x == 0) rp->b = b_est;
     }
     // power-of-4 sizes (4096 for C3 / C4): in-place radix-4 DIT on one LDS buffer, the inputs stored
     // at their base-4 digit-reversed positions (ip); otherwise the two-buffer Stockham passes
@@ -1620,14 +1651,16 @@ __global__ void __launch_bounds__(SYNC_FINE_THREADS) __attribute__((amdgpu_waves
     const uint32_t nbuf = r8 ? R8_SLOTS : ip ? nf + nf / 32 : nf;  // (the host sizes the LDS the same way)
     float2* xb = smem + 16;
     float2* yb = xb + nbuf;
-    // the forward spectrum is read once per template: kept in a global scratch row (L2-resident
-    // while the workgroup runs) instead of a third LDS buffer, for two workgroups per CU
+    // the forward spectrum is read once per template: kept in a global scratch row of this workgroup
+    // (L2-resident while it runs) instead of a third LDS buffer, for two workgroups per CU
     float2* Sb = A.spec + static_cast<size_t>(blockIdx.x) * nf;
-    // strongest antenna: first maximum of coarse_peak_array (ant.cpp:104-108)
-    uint32_t best = 0;
-    for (uint32_t a = 1; a < A.n_ant; ++a)
-        if (rp->coarse_metric[a] > rp->coarse_metric[best]) best = a;
-    const float cfo_hw = (rp->cfo_frac + rp->cfo_int) * static_cast<float>(A.Mtx) / static_cast<float>(A.Ltx);
+    if constexpr (!ALL) {
+        // strongest antenna: first maximum of coarse_peak_array (ant.cpp:104-108)
+        for (uint32_t a = 1; a < A.n_ant; ++a)
+            if (rp->coarse_metric[a] > rp->coarse_metric[best]) best = a;
+        cfo_frac = rp->cfo_frac;
+    }
+    const float cfo_hw = (cfo_frac + rp->cfo_int) * static_cast<float>(A.Mtx) / static_cast<float>(A.Ltx);
     const int64_t base = rp->coarse_64 - static_cast<int64_t>(A.xc_l);
     const uint32_t stage_len = A.xc_len - 1 + A.tmpl_len;
     const float2* x = A.iq + w * A.win_stride + best * A.ant_stride;
@@ -1712,6 +1745,13 @@ __global__ void __launch_bounds__(SYNC_FINE_THREADS) __attribute__((amdgpu_waves
     if (threadIdx.x == 0) {
         const float* xm = s_val + 8;
         const uint32_t* xi = s_idx + 8;
+        if constexpr (ALL) {
+            for (uint32_t k = 0; k < 4; ++k) {
+                A.fine_m[(size_t(rep) * 8 + best) * 4 + k] = k < A.n_templates ? xm[k] : 0.f;
+                A.fine_i[(size_t(rep) * 8 + best) * 4 + k] = k < A.n_templates ? xi[k] : 0u;
+            }
+            return;
+        }
         uint32_t kbest = 0;
         float msum_max = 0.f;
         for (uint32_t k = 0; k < A.n_templates; ++k)
@@ -1728,6 +1768,55 @@ __global__ void __launch_bounds__(SYNC_FINE_THREADS) __attribute__((amdgpu_waves
         rp->fine_local = static_cast<uint32_t>(roundf(wi / msum_max));
         rp->fine_64 = base + rp->fine_local;
     }
+}
+
+__global__ void __launch_bounds__(SYNC_FINE_THREADS) __attribute__((amdgpu_waves_per_eu(DNRP_FINE_WPE))) sync_fine_kernel(sync_args A) {
+    sync_fine_body<false>(A);
+}
+
+// every antenna with a coarse peak (sync_args::fine_all): grid n * max_reports * n_ant, the LDS of sync_fine_kernel
+__global__ void __launch_bounds__(SYNC_FINE_THREADS) __attribute__((amdgpu_waves_per_eu(DNRP_FINE_WPE))) sync_fine_ant_kernel(sync_args A) {
+    sync_fine_body<true>(A);
+}
+
+// crosscorrelator.cpp:205-248 on sync_fine_ant_kernel's table, one thread per report, its own launch (the
+// sums run in ascending antenna order whatever the scheduling of the search workgroups): per template the
+// metric sum and the metric-weighted mean index, N_eff_TX of the first largest sum, the fine peak the
+// index of that template; and the report's CFO and b, which the one-workgroup form writes in its search.
+constexpr uint32_t SYNC_COMBINE_THREADS = 64;
+__global__ void __launch_bounds__(SYNC_COMBINE_THREADS) sync_fine_combine_kernel(sync_args A, uint32_t n_rep) {
+    const uint32_t rep = blockIdx.x * SYNC_COMBINE_THREADS + threadIdx.x;
+    if (rep >= n_rep) return;
+    sync_res* rp = A.res + rep;
+    if (!rp->found) return;
+    rp->cfo_frac = sync_cfo_frac(A, rp, rep);
+    if (A.beta_on) rp->b = sync_beta_decide(A, A.band + size_t(rep) * 8 * SYNC_BANDS);
+    float ms[4] = {0.f, 0.f, 0.f, 0.f}, wi[4] = {0.f, 0.f, 0.f, 0.f};
+    for (uint32_t a = 0; a < A.n_ant; ++a) {
+        if (!(rp->coarse_metric[a] > 0.f)) continue;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const float m = A.fine_m[(size_t(rep) * 8 + a) * 4 + k];  // 0 for k >= n_templates
+            ms[k] += m;
+            wi[k] += m * static_cast<float>(A.fine_i[(size_t(rep) * 8 + a) * 4 + k]);
+        }
+    }
+    uint32_t kbest = 0, ibest = 0;
+    float msum_max = 0.f;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t idx = k < A.n_templates && ms[k] > 0.f ? static_cast<uint32_t>(roundf(wi[k] / ms[k])) : 0u;
+        rp->xc_metric[k] = k < A.n_templates ? ms[k] : 0.f;
+        rp->xc_idx[k] = idx;
+        if (k < A.n_templates && msum_max < ms[k]) {  // strictly larger (crosscorrelator.cpp:218-233)
+            msum_max = ms[k];
+            kbest = k;
+            ibest = idx;
+        }
+    }
+    rp->N_eff_TX = 1u << kbest;
+    rp->fine_local = ibest;
+    rp->fine_64 = rp->coarse_64 - static_cast<int64_t>(A.xc_l) + ibest;
 }
 
 // ===================================================================== launchers
@@ -1959,7 +2048,14 @@ hipError_t launch_sync_fine(const sync_args& a, uint32_t n, hipStream_t st) {
     const size_t nbuf = size_t(1) << a.log2_fft;
     // in place: one padded buffer (radix 8 at 4096 points: R8_SLOTS)
     const size_t lds = (16 + (DNRP_FINE_R8 && a.log2_fft == 12 ? R8_SLOTS : (a.log2_fft & 1u) == 0 ? nbuf + nbuf / 32 : 2 * nbuf)) * sizeof(float2);
-    hipLaunchKernelGGL(sync_fine_kernel, dim3(n * a.max_reports), dim3(SYNC_FINE_THREADS), lds, st, a);
+    if (!a.fine_all) {
+        hipLaunchKernelGGL(sync_fine_kernel, dim3(n * a.max_reports), dim3(SYNC_FINE_THREADS), lds, st, a);
+        return hipGetLastError();
+    }
+    const uint32_t n_rep = n * a.max_reports;
+    hipLaunchKernelGGL(sync_fine_ant_kernel, dim3(n_rep * a.n_ant), dim3(SYNC_FINE_THREADS), lds, st, a);
+    hipLaunchKernelGGL(sync_fine_combine_kernel, dim3((n_rep + SYNC_COMBINE_THREADS - 1) / SYNC_COMBINE_THREADS),
+                       dim3(SYNC_COMBINE_THREADS), 0, st, a, n_rep);
     return hipGetLastError();
 }
 

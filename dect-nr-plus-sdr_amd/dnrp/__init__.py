@@ -196,7 +196,8 @@ EXPORTS = ["dnrp_ctx_create", "dnrp_ctx_destroy", "dnrp_add_network_id", "dnrp_g
            "dnrp_harq_rx_destroy", "dnrp_pdc_decode_batch", "dnrp_pdc_encode_batch",
            "dnrp_pcc_decode_batch", "dnrp_pdc_decode_batch_harq", "dnrp_pdc_softbuffer_size",
            "dnrp_pcc_encode_batch", "dnrp_query_table", "dnrp_ctx_set_rx_mode", "dnrp_ctx_set_tx_windowing",
-           "dnrp_tx_window", "dnrp_ctx_set_sync_beta_search", "dnrp_ctx_get_sync_beta_search"]
+           "dnrp_tx_window", "dnrp_ctx_set_sync_beta_search", "dnrp_ctx_get_sync_beta_search",
+           "dnrp_ctx_set_sync_fine_all_antennas", "dnrp_ctx_get_sync_fine_all_antennas", "dnrp_rx_sync_fine_peaks"]
 
 _lib = None
 
@@ -227,6 +228,9 @@ def lib():
         L.dnrp_tx_window.argtypes = [C.c_uint32, C.c_float, P, C.c_uint32]
         L.dnrp_ctx_set_sync_beta_search.argtypes = [P, C.c_uint32, C.c_float]
         L.dnrp_ctx_get_sync_beta_search.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.dnrp_ctx_set_sync_fine_all_antennas.argtypes = [P, C.c_uint32]
+        L.dnrp_ctx_get_sync_fine_all_antennas.argtypes = [P, C.POINTER(C.c_uint32)]
+        L.dnrp_rx_sync_fine_peaks.argtypes = [P, C.c_uint32, P, P, P]
         L.dnrp_ring_gather.argtypes = [P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, P, C.c_uint32, P, P]
         L.dnrp_channel_batch.argtypes = [P, C.POINTER(ChannelCfg), C.c_uint32, C.c_uint32, P, C.c_uint32, C.c_uint32, P, P,
                                          P, C.c_uint32, P]
@@ -450,6 +454,30 @@ class Phy:
         _chk(lib().dnrp_ctx_get_sync_beta_search(self._ctx, C.byref(on), C.byref(db), C.byref(lin)),
              "dnrp_ctx_get_sync_beta_search")
         return bool(on.value), db.value, lin.value
+
+    def set_sync_fine_all_antennas(self, on):
+        """dnrp_ctx_set_sync_fine_all_antennas: every later rx_sync_batch / rx_sync_stream cross-correlates every
+        searched antenna that has a coarse peak against the STF templates and combines the peaks by their
+        metrics (the reference's build option RX_SYNC_PARAM_CROSSCORRELATOR_ALL_ANTENNAS_OR_ONLY_STRONGEST);
+        off (the default) searches the strongest antenna only."""
+        _chk(lib().dnrp_ctx_set_sync_fine_all_antennas(self._ctx, int(on)), "dnrp_ctx_set_sync_fine_all_antennas")
+
+    def sync_fine_all_antennas(self):
+        """dnrp_ctx_get_sync_fine_all_antennas"""
+        on = C.c_uint32()
+        _chk(lib().dnrp_ctx_get_sync_fine_all_antennas(self._ctx, C.byref(on)), "dnrp_ctx_get_sync_fine_all_antennas")
+        return bool(on.value)
+
+    def sync_fine_peaks(self, n_reports, stream=None):
+        """dnrp_rx_sync_fine_peaks: (metric float32, index uint32), each [n_reports, 8, 4] = (report slot of the
+        latest rx_sync_batch in res order, antenna, template), 0 where not processed; n_reports = n * max_reports
+        of that call, which ran with set_sync_fine_all_antennas(1). Synchronises the stream before it returns."""
+        metric = np.zeros((n_reports, 8, 4), np.float32)
+        index = np.zeros((n_reports, 8, 4), np.uint32)
+        _chk(lib().dnrp_rx_sync_fine_peaks(self._ctx, int(n_reports), C.c_void_p(metric.ctypes.data),
+                                           C.c_void_p(index.ctypes.data), _stream_ptr(stream)), "dnrp_rx_sync_fine_peaks")
+        self.sync(stream)
+        return metric, index
 
     def add_network_id(self, nid):
         _chk(lib().dnrp_add_network_id(self._ctx, nid), "dnrp_add_network_id")

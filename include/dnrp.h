@@ -51,7 +51,8 @@ extern "C" {
 #define DNRP_ENOMEM (-4)      /* device allocation failed / batch larger than max_batch */
 #define DNRP_EDEVICE (-5)     /* HIP runtime error */
 #define DNRP_ENETID (-6)      /* network ID not registered with dnrp_add_network_id */
-#define DNRP_ESTATE (-7)      /* dnrp_rx_pdc_batch without a preceding dnrp_rx_pcc_batch */
+#define DNRP_ESTATE (-7)      /* dnrp_rx_pdc_batch without a preceding dnrp_rx_pcc_batch; dnrp_rx_sync_fine_peaks
+                                 without a preceding dnrp_rx_sync_batch that ran with the setting on */
 
 typedef struct dnrp_ctx dnrp_ctx;
 
@@ -254,6 +255,45 @@ int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32_t n, const
  */
 int dnrp_ctx_set_sync_beta_search(dnrp_ctx* ctx, uint32_t on, float threshold_db);
 int dnrp_ctx_get_sync_beta_search(const dnrp_ctx* ctx, uint32_t* on, float* threshold_db, float* threshold_linear);
+
+/*
+ * Fine search over every antenna that has a coarse peak <- the build option
+ * RX_SYNC_PARAM_CROSSCORRELATOR_ALL_ANTENNAS_OR_ONLY_STRONGEST
+ * (lib/include/dectnrp/phy/rx/sync/sync_param.hpp:286; crosscorrelator_t::run_fine_search,
+ * lib/src/phy/rx/sync/crosscorrelator.cpp:122-249).
+ *   on  0 (default): exactly the synchronisation without the option: the antenna with the largest
+ *       coarse_peak_array entry is cross-correlated against the STF templates, the same launch, byte-identical
+ *       reports.
+ *       1: for every later dnrp_rx_sync_batch and dnrp_rx_sync_stream of the context (no context rebuild) every
+ *       searched antenna whose coarse_peak_array entry is > 0 is cross-correlated against every template
+ *       (crosscorrelator.cpp:137-147, 165-203), and of a report
+ *         fine_peak_metric[k]   is the reference's metric_sum of template k: the float sum of the processed
+ *                               antennas' metrics in ascending antenna order (crosscorrelator.cpp:221-226);
+ *         fine_peak_index[k]    roundf(sum_a metric[a][k] index[a][k] / metric_sum[k]), relative to the search
+ *                               start coarse_peak_time - search_left as before, rounded once;
+ *         N_eff_TX              1 << argmax_k metric_sum[k], strictly greater from 0, so the first template of a
+ *                               tie (crosscorrelator.cpp:218-233);
+ *         fine_peak_time_local  fine_peak_index[k_likely] (crosscorrelator.cpp:239-248), and fine_peak_time =
+ *                               coarse_peak_time - search_left + fine_peak_time_local.
+ *       Every other field, and the number and order of the reports, is as with the setting off (the search
+ *       goes on from the coarse peak). With one searched antenna the reports equal the off path's bit for bit.
+ *       Independent of dnrp_ctx_set_sync_beta_search: with both on every antenna is correlated against the
+ *       template rows of the decided b.
+ * DNRP_EINVAL for a NULL context or on > 1. The getter's output may be NULL.
+ *
+ * dnrp_rx_sync_fine_peaks: stream-ordered copy of the per-antenna peaks (peak_vec, crosscorrelator.cpp:195-201)
+ * of the context's latest dnrp_rx_sync_batch, which must have run with the setting on. metric and index are
+ * host arrays [n_reports][8][4] ordered (report slot in `res` order, antenna, template); n_reports must equal
+ * that call's n * max_reports. index is relative to the search start. Entries of antennas that were not
+ * processed are 0: antennas without a coarse peak, antennas >= N_ant_limited, templates the class does not
+ * have, slots not `found`. Valid once `stream` has been synchronised. Not offered for dnrp_rx_sync_stream,
+ * which filters and reorders the reports of its chunks: after it the call returns DNRP_ESTATE.
+ * DNRP_ESTATE if the latest sync call ran with the setting off or there was none; DNRP_EINVAL for a NULL
+ * pointer or another n_reports.
+ */
+int dnrp_ctx_set_sync_fine_all_antennas(dnrp_ctx* ctx, uint32_t on);
+int dnrp_ctx_get_sync_fine_all_antennas(const dnrp_ctx* ctx, uint32_t* on);
+int dnrp_rx_sync_fine_peaks(dnrp_ctx* ctx, uint32_t n_reports, float* metric, uint32_t* index, void* stream);
 
 /*
  * RX phase 1: synchronised PCC demodulation of n packets. Each packet is processed with the
