@@ -223,6 +223,9 @@ int dnrp_tx_window(uint32_t N_b_DFT_os, float fraction, float* rising, uint32_t 
  *   iq       device cf32; window w, antenna a, sample i at iq[2*(w*win_stride + a*ant_stride + i)]
  *            (strides in samples: [n][N_RX][S] windows or per-antenna continuous streams)
  *   res      host [n][max_reports]; n_found host [n] (optional). Valid after dnrp_sync().
+ * DNRP_EUNSUPPORTED for a sync geometry (sc->u, sc->b with the context's os_min, L and M) whose detection
+ * staging or whose fine search (two buffers of the power of two >= xc_len - 1 + tmpl_len points) exceeds
+ * 160 KiB of LDS, e.g. (u 2, b 16) at os_min 2 and 40/27: nothing is queued, the context stays usable.
  */
 int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32_t n, const float* iq, uint64_t win_stride,
                        uint64_t ant_stride, uint32_t S_win, dnrp_sync_result* res, uint32_t* n_found, void* stream);

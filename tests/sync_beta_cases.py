@@ -24,7 +24,9 @@ PARITY = [(1, 4, 1, 1, 1, 1, 0, 1), (1, 4, 1, 1, 1, 1, 0, 2), (1, 4, 1, 1, 1, 1,
           (1, 2, 2, 1, 1, 2, 1, 1)]
 # no oracle search with these filters / ratios: checked against the transmitted truth
 TRUTH = [(1, 4, 1, 10, 9, 2, 1, 1), (1, 4, 1, 10, 9, 2, 1, 2), (2, 8, 1, 10, 9, 4, 5, 2),
-         (1, 12, 1, 40, 27, 1, 0, 8), (1, 12, 1, 1, 1, 1, 0, 8), (1, 12, 1, 1, 1, 1, 0, 12)]
+         (1, 12, 1, 40, 27, 1, 0, 8), (1, 12, 1, 1, 1, 1, 0, 8), (1, 12, 1, 1, 1, 1, 0, 12),
+         # os_min 2 at 10/9: sync_beta_kernel<9, 10, 4>
+         (1, 2, 2, 10, 9, 2, 1, 1), (1, 2, 2, 10, 9, 2, 1, 2)]
 N_WINDOWS = 2
 
 

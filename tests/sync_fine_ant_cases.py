@@ -25,7 +25,8 @@ CASES = [(1, 1, 1, 1, 1, 2, 1),     # 256-point, in-place radix 4
          (1, 2, 1, 1, 1, 2, 1),     # 512-point, Stockham
          (1, 4, 1, 10, 9, 4, 5),    # resampled stream, four antennas, three templates
          (1, 16, 1, 1, 1, 2, 1),    # 4096-point radix-8 form of C3 / C4
-         (2, 8, 1, 1, 1, 8, 10)]    # eight antennas, four templates
+         (2, 8, 1, 1, 1, 8, 10),    # eight antennas, four templates
+         (2, 12, 2, 10, 9, 2, 1)]   # 8192-point Stockham (131 KB of LDS per workgroup), os_min 2
 FOUR = CASES[2]
 # variants of FOUR: per-antenna delay in hw samples, per-antenna SNR in dB against the antenna's own packet
 # power (None: the common 30 dB against the mean power), the antenna that carries noise only
