@@ -72,30 +72,84 @@ __device__ __forceinline__ void stage_span_lo(float2* dst, const float2* __restr
     });
 }
 
-// stage_span_lo for one wavefront whose whole span [q0, q0 + n] lies inside the valid range: two
-// samples per lane and load (16 B, 8-B aligned: the unaligned dwordx4 form, nontemporal), half the load
-// instructions of the float2 form and 16-B LDS writes; x[q0 + n] may be read, never written
+// A buffer descriptor over [p, p + bytes) of a wave-uniform row. The pointer halves and the size pass
+// through readfirstlane, so the descriptor sits in scalar registers also where the row index came from
+// threadIdx (a wave id): no per-access waterfall loop. Loads past the range return zero, stores are dropped.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void* p, uint32_t bytes) {
+    const uintptr_t v = reinterpret_cast<uintptr_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(uintptr_t(lo) | uintptr_t(hi) << 32), 0,
+                                             static_cast<int>(__builtin_amdgcn_readfirstlane(bytes)), 0x00020000);
+}
+
+constexpr uint32_t ROW_SPAN_MAX = 1u << 28;  // float2 elements of a row behind a span descriptor (2 GiB)
+
+// stage_span_lo for one wavefront through a buffer descriptor: dst[i] = row[p0 + i], i in [0, n), zero
+// where p0 + i lies outside [v0, S) (v0 <= S <= ROW_SPAN_MAX). The descriptor covers the valid samples
+// the span needs and nothing else, so the hardware range check replaces the per-element 64-bit
+// compares and the loads need no 64-bit lane address. All bounds are wave-uniform (scalar arithmetic).
+// Spans with one sample to spare inside the valid range take 16-B loads of two samples per lane (8-B
+// aligned, nontemporal: bypasses only the L1, the samples are not re-read by this wave), the descriptor
+// ending on a pair boundary so that no load straddles its end; element n may be read, never written.
+// The others (a packet at an edge of its window) take 8-B loads, a sample before v0 at an offset past
+// the range.
 template <int U>
-__device__ __forceinline__ void stage_span_x2(float2* dst, const float2* __restrict__ x, int64_t q0, uint32_t n,
-                                              uint32_t lane) {
-    for (uint32_t base = 0; base < n; base += 128 * U) {
+__device__ __forceinline__ void stage_span_row(float2* dst, const float2* __restrict__ row, int64_t p0, uint32_t n,
+                                               int64_t v0, int64_t S, uint32_t lane) {
+    typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+    typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+    const int64_t e064 = p0 - v0;  // the span's first sample relative to the first valid one
+    const int64_t lim = static_cast<int64_t>(ROW_SPAN_MAX);
+    const int e0 = __builtin_amdgcn_readfirstlane(static_cast<int>(e064 < -lim ? -lim : e064 > lim ? lim : e064));
+    const int nv = __builtin_amdgcn_readfirstlane(static_cast<int>(S - v0 < 0 ? 0 : S - v0 > lim ? lim : S - v0));  // valid samples
+    if (e0 >= 0 && e0 + static_cast<int>(n) < nv) {
+        const uint32_t npair = (n + 1) & ~1u;
+        const __amdgpu_buffer_rsrc_t rs = row_rsrc(row + v0 + e0, npair * 8u);
+        const bool full = n >= 128u * (U - 1);
         float4 v[U];
 #pragma unroll
         for (int j = 0; j < U; ++j) {
-            const uint32_t i = base + 2 * lane + 128 * j;
-            v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            // nontemporal: bypasses only the L1, the samples are not re-read by this wave
-            typedef float f4u __attribute__((ext_vector_type(4), aligned(8)));
-            if (i < n) {
-                const f4u t = __builtin_nontemporal_load(reinterpret_cast<const f4u*>(x + q0 + i));
-                v[j] = make_float4(t.x, t.y, t.z, t.w);
-            }
+            const u4v t = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16u + 1024u * j, 0, 2);
+            v[j] = make_float4(__uint_as_float(t.x), __uint_as_float(t.y), __uint_as_float(t.z), __uint_as_float(t.w));
         }
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const uint32_t i = base + 2 * lane + 128 * j;
+        auto put = [&](int j) {  // the span's last pair may be half a pair, later ones lie past it
+            const uint32_t i = 2 * lane + 128 * j;
             if (i + 1 < n) *reinterpret_cast<float4*>(dst + i) = v[j];
             else if (i < n) dst[i] = make_float2(v[j].x, v[j].y);
+        };
+        if (full) {  // every load but the last lies inside the span: no per-lane tests
+#pragma unroll
+            for (int j = 0; j < U - 1; ++j) *reinterpret_cast<float4*>(dst + 2 * lane + 128 * j) = v[j];
+            put(U - 1);
+        } else {
+#pragma unroll
+            for (int j = 0; j < U; ++j) put(j);
+        }
+        for (uint32_t base = 128u * U; base < n; base += 128u) {  // spans longer than U loads per lane
+            const uint32_t i = base + 2 * lane;
+            const u4v t = __builtin_amdgcn_raw_buffer_load_b128(rs, i * 8u, 0, 2);
+            if (i + 1 < n) *reinterpret_cast<float4*>(dst + i) = make_float4(__uint_as_float(t.x), __uint_as_float(t.y), __uint_as_float(t.z), __uint_as_float(t.w));
+            else if (i < n) dst[i] = make_float2(__uint_as_float(t.x), __uint_as_float(t.y));
+        }
+        return;
+    }
+    // edge: the descriptor starts at the first valid sample and ends with the span or the valid range
+    const int64_t end = static_cast<int64_t>(e0) + n;
+    const uint32_t ne = static_cast<uint32_t>(end < 0 ? 0 : end > nv ? nv : end);
+    const __amdgpu_buffer_rsrc_t rs = row_rsrc(row + (nv ? v0 : 0), ne * 8u);  // (no valid sample: empty)
+    for (uint32_t base = 0; base < n; base += 64u * 2 * U) {
+        float2 v[2 * U];
+#pragma unroll
+        for (int j = 0; j < 2 * U; ++j) {
+            const int e = e0 + static_cast<int>(base + lane + 64 * j);
+            const u2v t = __builtin_amdgcn_raw_buffer_load_b64(rs, e >= 0 ? static_cast<uint32_t>(e) * 8u : 0x80000000u, 0, 0);
+            v[j] = make_float2(__uint_as_float(t.x), __uint_as_float(t.y));
+        }
+#pragma unroll
+        for (int j = 0; j < 2 * U; ++j) {
+            const uint32_t i = base + lane + 64 * j;
+            if (i < n) dst[i] = v[j];
         }
     }
 }

@@ -654,8 +654,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) rx
     float2* R = smem;
     const rx_pkt_in in = A.pin[pkt];
     const rx_pkt_state S = A.st[pkt];
-    const int64_t q_hi = static_cast<int64_t>(A.S_in) - in.fine_peak, q_lo = in.fine_peak < 0 ? -in.fine_peak : 0;
-    const float2* src = A.iq + (size_t(in.win) * A.N_RX + a) * A.S_in + in.fine_peak;
+    // valid samples of the window row: from the fine peak (zero history before it), or from the row's
+    // start where the packet begins before the window, to the row's end
+    const int64_t v0 = in.fine_peak < 0 ? 0 : in.fine_peak;
+    const float2* srow = A.iq + (size_t(in.win) * A.N_RX + a) * A.S_in;
     const float2 w1_ = wfft_tw<-1>(A.tw, 4 * (lane0 & 15u)), wl_ = wfft_tw<-1>(A.tw, lane0);
     const bool to_y = !experiment(XS_FE_SKIP_STORE) && !A.no_y;
 #pragma unroll 1
@@ -675,12 +677,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) rx
         }
         const rx_span_t sp = rx_span<LR, MR, HLR>(A, l);
         if (i) __builtin_amdgcn_wave_barrier();  // the previous symbol's reads of R are done
-        if constexpr (!experiment(XS_FE_SKIP_LOAD)) {
-            if (sp.in0 >= q_lo && sp.in0 + sp.n_in < q_hi)  // the span and one sample past it inside the window
-                stage_span_x2<10>(R, src, sp.in0, sp.n_in, lane);
-            else
-                stage_span_lo<20>(R, src, sp.in0, sp.n_in, q_lo, q_hi, lane, 64);
-        }
+        if constexpr (!experiment(XS_FE_SKIP_LOAD))
+            stage_span_row<10>(R, srow, in.fine_peak + sp.in0, sp.n_in, v0, A.S_in, lane);
         __builtin_amdgcn_wave_barrier();
         // the next symbol's span into the caches while this one is computed: one dword per 128-B line
         // (two lines per lane), issued after this span's loads have landed and consumed at the end of
@@ -689,6 +687,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) rx
         float pf0 = 0.f, pf1 = 0.f;
         if (experiment(XS_FE_PREFETCH) && i + 1 < SPW && li + 1 < A.sym_count) {
             const rx_span_t sn = rx_span<LR, MR, HLR>(A, A.sym_list ? A.sym_list[li + 1] : l + 1);
+            const int64_t q_hi = static_cast<int64_t>(A.S_in) - in.fine_peak, q_lo = v0 - in.fine_peak;
+            const float2* src = srow + in.fine_peak;
             const int64_t lo = max<int64_t>(sn.in0, q_lo), hi = min<int64_t>(sn.in0 + sn.n_in, q_hi) - 1;
             if (hi >= lo) {
                 const float* f = reinterpret_cast<const float*>(src);
@@ -696,18 +696,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) rx
                 pf1 = f[2 * min<int64_t>(lo + 16 * (lane + 64), hi)];
             }
         }
-        float2* Yrow = A.Y + ((size_t(pkt) * A.N_RX + a) * A.n_sym_total + l) * A.Nf_pad;
+        // the symbol's Y row behind a descriptor (uniform base in scalar registers, stores at k * 8)
+        const __amdgpu_buffer_rsrc_t yr =
+            row_rsrc(A.Y + ((size_t(pkt) * A.N_RX + a) * A.n_sym_total + l) * A.Nf_pad, to_y ? A.Nf_pad * 8u : 0u);
         const bool drs = so != 0xFFFFu;
         if constexpr (!experiment(XS_FE_SKIP_FIR)) rx_resample_ct<LR, MR, HLR>(A, in, S, sp, R, lane);
         rx_fft_bins<true>(A, S, R, lane, [&](uint32_t k, float2 v) {
             // Y is written once and read by the next launch: nontemporal stores when that launch
             // comes after the whole batch, plain ones when it follows within a cache-sized group
-            typedef float f2v __attribute__((ext_vector_type(2)));
-            if constexpr (YNT) {
-                if (to_y) __builtin_nontemporal_store(f2v{v.x, v.y}, reinterpret_cast<f2v*>(Yrow + k));
-            } else {
-                if (to_y) Yrow[k] = v;
-            }
+            typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+            if (to_y) __builtin_amdgcn_raw_buffer_store_b64(u2v{__float_as_uint(v.x), __float_as_uint(v.y)}, yr, k * 8u, 0, YNT ? 2 : 0);
             if (drs) R[k] = v;
         }, w1, wl);
         if (drs) {
@@ -771,6 +769,7 @@ hipError_t launch_rx_fft(const rx_front_args& a_in, uint32_t n, hipStream_t st) 
             // chunk, same box)
             const size_t lds1 = size_t(rxw_region(9, 10, W)) * sizeof(float2);
             const dim3 gs(n * a.N_RX * ((a.sym_count + DNRP_RX_SPW - 1) / DNRP_RX_SPW));
+            if (DNRP_RX_SPW > 1 && a.S_in > ROW_SPAN_MAX) return hipErrorInvalidValue;  // the span descriptor's range
             if (DNRP_RX_SPW > 1 && a.y_plain)
                 hipLaunchKernelGGL((rx_fft_wave_ct_kernel<DNRP_RX_SPW, false>), gs, dim3(64), lds1, st, a);
             else if (DNRP_RX_SPW > 1)

@@ -285,13 +285,14 @@ __global__ void __launch_bounds__(CELL_THREADS) rx_cells_kernel(rx_cells_args A)
     unit_a na;
     unit_b<NRX, NT> cur;
     uint32_t u = tid;
+    const __amdgpu_buffer_rsrc_t yr = y_rows(A, Yp);
     unit_stage_a(A, sg, nseg, si, u, per_unit, na);
-    unit_stage_b<NRX, NT>(A, sg, pairs, Yp, seq, na, cur);
+    unit_stage_b<NRX, NT>(A, sg, pairs, yr, seq, na, cur);
     if (u + CELL_THREADS < units) unit_stage_a(A, sg, nseg, si, u + CELL_THREADS, per_unit, na);
     for (; u < units; u += CELL_THREADS) {
         unit_b<NRX, NT> nb;
         const bool m1 = u + CELL_THREADS < units, m2 = u + 2 * CELL_THREADS < units;
-        if (m1) unit_stage_b<NRX, NT>(A, sg, pairs, Yp, seq, na, nb);
+        if (m1) unit_stage_b<NRX, NT>(A, sg, pairs, yr, seq, na, nb);
         if (m2) unit_stage_a(A, sg, nseg, si, u + 2 * CELL_THREADS, per_unit, na);
         eq_compute<NRX, NT, NBPS>(A, sg, zfi, wtab, zst, cur, llr);
         if (m1) cur = nb;
@@ -300,7 +301,7 @@ __global__ void __launch_bounds__(CELL_THREADS) rx_cells_kernel(rx_cells_args A)
 
 hipError_t launch_rx_cells(const rx_cells_args& a, uint32_t n, hipStream_t st) {
     const size_t lds = cell_lds_bytes(a.N_RX, a.NT, a.n_drs, a.wcap[0], a.wcap[1]);
-    if (lds > 160 * 1024 || a.n_pkt != n) return hipErrorInvalidValue;
+    if (lds > 160 * 1024 || a.n_pkt != n || !y_rows_fit(a)) return hipErrorInvalidValue;
     const dim3 g((n + 7) / 8 * 8 * a.n_epochs), b(CELL_THREADS);
     // 256-QAM (N_bps = 8, the bench's C3 / C4) with the demapper width compiled in
 #define DNRP_CELLS(R, T)                                                                 \

@@ -60,7 +60,9 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
     const uint32_t pl = (xs / A.n_epochs) * 8 + (blockIdx.x & 7u), ep = xs % A.n_epochs;
     if (pl >= A.n_pkt) return;  // uniform per workgroup
     const uint32_t pkt = rx_slot_of(A.sel, pl), row = rx_row_of(A.sel, pl);
-    const uint32_t tid = threadIdx.x, w = tid >> 6;
+    // the wave index in a scalar register: the task loop's symbol, antenna, span bounds and row bases
+    // are then scalar arithmetic, and its control flow scalar branches
+    const uint32_t tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // ---- 1. front end of the epoch's symbols, task = (symbol, antenna), wave w takes w, w + 8, ...
     {
@@ -70,7 +72,9 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
         const uint32_t lane0 = tid & 63u;
         const rx_pkt_in in = F.pin[pkt];
         const rx_pkt_state S = F.st[pkt];
-        const int64_t q_hi = static_cast<int64_t>(F.S_in) - in.fine_peak, q_lo = in.fine_peak < 0 ? -in.fine_peak : 0;
+        // valid samples of a window row: from the fine peak (zero history before it, rx_synced.cpp:711-740),
+        // or from the row's start where the packet begins before the window, to the row's end
+        const int64_t v0 = in.fine_peak < 0 ? 0 : in.fine_peak;
         const float2 w1_ = wfft_tw<-1>(F.tw, 4 * (lane0 & 15u)), wl_ = wfft_tw<-1>(F.tw, lane0);
 #pragma unroll 1
         for (uint32_t t = w; t < ntask; t += EP_WAVES) {
@@ -79,18 +83,17 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
             float2 w1 = w1_, wl = wl_;
             asm volatile("" : "+v"(lane), "+v"(w1.x), "+v"(w1.y), "+v"(wl.x), "+v"(wl.y));
             const uint32_t ns = X.ep_off[ep + 1] - s0;
-            const uint32_t l = DNRP_EP_AMAJOR ? X.ep_sym[s0 + t % ns] : X.ep_sym[s0 + t / NRX];
+            const uint32_t l = __builtin_amdgcn_readfirstlane(DNRP_EP_AMAJOR ? X.ep_sym[s0 + t % ns] : X.ep_sym[s0 + t / NRX]);
             const uint32_t a = DNRP_EP_AMAJOR ? t / ns : t % NRX;
-            const float2* src = F.iq + (size_t(in.win) * NRX + a) * F.S_in + in.fine_peak;
+            const float2* srow = F.iq + (size_t(in.win) * NRX + a) * F.S_in;  // the (window, antenna) row
             const rx_span_t sp = rx_span<LR, MR, HLR>(F, l);
             if (t != w) __builtin_amdgcn_wave_barrier();  // the previous task's reads of R are done
-            if (sp.in0 >= q_lo && sp.in0 + sp.n_in < q_hi)
-                stage_span_x2<10>(R, src, sp.in0, sp.n_in, lane);
-            else
-                stage_span_lo<20>(R, src, sp.in0, sp.n_in, q_lo, q_hi, lane, 64);
+            stage_span_row<10>(R, srow, in.fine_peak + sp.in0, sp.n_in, v0, F.S_in, lane);
             __builtin_amdgcn_wave_barrier();
             rx_resample_ct<LR, MR, HLR>(F, in, S, sp, R, lane);
             const size_t yimg = experiment(XS_EP_SLOTY) ? blockIdx.x % (64u * A.n_epochs) : pkt;
+            // plain pointer stores: with the stores through a row descriptor (as in rx_fft_wave_ct_kernel) this
+            // kernel's build moved 2 of 4.4 million LLRs of a C4 chunk by one LSB (profiles/r09)
             float2* Yrow = F.Y + ((yimg * NRX + a) * F.n_sym_total + l) * F.Nf_pad;
             rx_fft_bins<true>(F, S, R, lane, [&](uint32_t k, float2 v) {
                 if constexpr (DNRP_EP_YNT) {
@@ -181,6 +184,7 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
     const uint32_t seq_hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(seqv >> 32));  // no sign extension)
     const uint8_t* __restrict__ seq = reinterpret_cast<const uint8_t*>(uintptr_t(seq_lo) | uintptr_t(seq_hi) << 32);
     int16_t* __restrict__ llr = A.llr + size_t(row) * A.llr_stride;
+    const __amdgpu_buffer_rsrc_t yr = y_rows(A, Yp);  // stage B's cell loads
     constexpr uint32_t per_unit = NT == 1 ? 1u : 2u;
     // Stage A two units ahead, stage B one step ahead of the equaliser (rx_eq.hpp). A plain unit is one
     // step. A twin unit (cell_seg::twin: the same subcarriers in symbols l and l + 1 of one event) is
@@ -198,7 +202,7 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
     // per subcarrier index (N_b_DFT_os = 1024), 12 for the symbol (host-checked where the plan has twins)
     auto pack_a = [](const unit_a& a) { return a.k0 | a.k1 << 10 | a.l << 20; };
     unit_stage_a(A, sg, nseg, si, u, per_unit, na);
-    unit_stage_b<NRX, NT>(A, sg, pairs, Yp, seq, na, cur);
+    unit_stage_b<NRX, NT>(A, sg, pairs, yr, seq, na, cur);
     uint32_t ca = pack_a(na);
     if (u + EP_THREADS < units) unit_stage_a(A, sg, nseg, si, u + EP_THREADS, per_unit, na);
     unit_merge_bits<NRX, NT>(N_bps, cur);
@@ -220,7 +224,7 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
                 sa.l = (ca >> 20) + 1;
             }
             const bool more = !last || m1;
-            if (more) unit_stage_b<NRX, NT>(A, sg, pairs, Yp, seq, sa, nb);
+            if (more) unit_stage_b<NRX, NT>(A, sg, pairs, yr, seq, sa, nb);
             if (last) {
                 ca = pack_a(na);
                 if (m2) unit_stage_a(A, sg, nseg, si, u + 2 * EP_THREADS, per_unit, na);
@@ -252,6 +256,7 @@ hipError_t launch_rx_epoch(const rx_epoch_args& x, uint32_t n, hipStream_t st) {
     const rx_cells_args& a = x.C;
     const size_t lds = rx_epoch_lds(a);
     if (lds > 160 * 1024 || a.n_pkt != n || x.F.plan.N != 1024 || !rx_epoch_supported(a.N_RX, a.NT)) return hipErrorInvalidValue;
+    if (x.F.S_in > ROW_SPAN_MAX || !y_rows_fit(a)) return hipErrorInvalidValue;  // the row descriptors' ranges
     const dim3 g((n + 7) / 8 * 8 * a.n_epochs), b(EP_THREADS);
 #define DNRP_EP(R, T)                                                                   \
     if (a.N_RX == R && a.NT == T) {                                                     \

@@ -116,9 +116,19 @@ __device__ __forceinline__ const __attribute__((address_space(1))) T* as_global(
     return reinterpret_cast<const __attribute__((address_space(1))) T*>(reinterpret_cast<uintptr_t>(p));
 }
 
+// the descriptor of a packet's Y rows [N_RX][n_sym_total][Nf_pad] (at most Y_ROWS_MAX bytes, checked at
+// the launch) for unit_stage_b
+constexpr uint64_t Y_ROWS_MAX = 0x7FFFFFFFull;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t y_rows(const rx_cells_args& A, const float2* Yp) {
+    return row_rsrc(Yp, A.N_RX * A.n_sym_total * A.Nf_pad * 8u);
+}
+__host__ inline bool y_rows_fit(const rx_cells_args& A) {
+    return uint64_t(A.N_RX) * A.n_sym_total * A.Nf_pad * 8u <= Y_ROWS_MAX;
+}
+
 template <int NRX, int NT>
 __device__ __forceinline__ void unit_stage_b(const rx_cells_args& A, const cell_seg* sg, const uint32_t* pairs,
-                                             const float2* __restrict__ Yp, const uint8_t* __restrict__ seq,
+                                             __amdgpu_buffer_rsrc_t Yr, const uint8_t* __restrict__ seq,
                                              const unit_a& a, unit_b<NRX, NT>& b) {
     const uint32_t Nf = A.N_occ + 1;
     const cell_seg& S = sg[a.si];
@@ -138,29 +148,35 @@ __device__ __forceinline__ void unit_stage_b(const rx_cells_args& A, const cell_
         b.pw[2] = spw[((tB & 3u) ^ swap) * Nf + a.k0];
         b.pw[3] = spw[((tB & 3u) ^ swap) * Nf + a.k1];
     }
-    const size_t ast = size_t(A.n_sym_total) * A.Nf_pad;
+    // the packet's Y rows through their descriptor (y_rows): the cell's byte offset in its antenna
+    // image per lane (32 bits), the antenna image's offset uniform in a scalar register
+    typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+    typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+    const uint32_t ast8 = A.n_sym_total * A.Nf_pad * 8u;
     const uint32_t yoff = a.l * A.Nf_pad;
+    auto cell = [&](int r, uint32_t k) {
+        const u2v v = __builtin_amdgcn_raw_buffer_load_b64(Yr, (yoff + k) * 8u, r * ast8, 0);
+        return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
+    };
     if constexpr (NT > 1) {
         // the pair's two cells are neighbours except across DC: one 16-B load per antenna (8-B
-        // aligned: unaligned dwordx4, k0 + 1 <= N_b_OCC < Nf_pad stays in the row), the DC pair's
-        // second cell reloaded. Nontemporal, so that it stays one dwordx4: a plain load with the DC
-        // reload behind it is sunk into an 8-B load plus two 4-B loads from a selected address (the
-        // cells are read once; nt loads bypass only the L1)
-        typedef float f4u __attribute__((ext_vector_type(4), aligned(8)));
+        // aligned, k0 + 1 <= N_b_OCC < Nf_pad stays in the row), the DC pair's second cell reloaded.
+        // Nontemporal as the global load it replaces (the cells are read once; nt loads bypass only
+        // the L1)
         const bool dc = a.k1 != a.k0 + 1;
 #pragma unroll
         for (int r = 0; r < NRX; ++r) {
-            const f4u v = __builtin_nontemporal_load(reinterpret_cast<const f4u*>(Yp + r * ast + yoff + a.k0));
-            b.r0[r] = make_float2(v.x, v.y);
-            b.r1[r] = make_float2(v.z, v.w);
+            const u4v v = __builtin_amdgcn_raw_buffer_load_b128(Yr, (yoff + a.k0) * 8u, r * ast8, 2);
+            b.r0[r] = make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
+            b.r1[r] = make_float2(__uint_as_float(v.z), __uint_as_float(v.w));
         }
         if (dc) {
 #pragma unroll
-            for (int r = 0; r < NRX; ++r) b.r1[r] = Yp[r * ast + yoff + a.k1];
+            for (int r = 0; r < NRX; ++r) b.r1[r] = cell(r, a.k1);
         }
     } else {
 #pragma unroll
-        for (int r = 0; r < NRX; ++r) b.r0[r] = Yp[r * ast + yoff + a.k0];
+        for (int r = 0; r < NRX; ++r) b.r0[r] = cell(r, a.k0);
     }
     // the unit's scrambling bits [jj N_bps, (jj + cells) N_bps) lie in at most 3 bytes
     // (loads clamped to the last byte and kept raw: nothing here waits on the loads in flight)
