@@ -302,6 +302,8 @@ struct dnrp_ctx {
     // TX OFDM windowing (dnrp_ctx_set_tx_windowing): the fraction of later TX calls (0: off) and the
     // rising edges uploaded so far, one per (N_b_DFT_os, fraction bits)
     float tx_win_fraction = 0.0f;
+    dnrp::dev::tx_form tx_form{};  // kernel form of the latest dnrp_tx_batch that launched (dnrp_tx_last_form)
+    bool tx_form_valid = false;
     std::map<std::pair<uint32_t, uint32_t>, std::unique_ptr<dbuf>> tx_win;
     dbuf stf_part;  // [max_batch][8] double2 cs | [max_batch][8] float rms | [max_batch][8][14 b_max] float2 cells
     dbuf snr_part;  // [slot][n_sym_total][N_RX][8] double2: front-end DRS SNR partial sums

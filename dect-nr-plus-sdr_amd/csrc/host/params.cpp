@@ -192,6 +192,9 @@ int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, floa
                     wcap[mode] = std::max(wcap[mode], (static_cast<uint32_t>(L.weights.size()) + 3u) & ~3u);
                 }
             v.push_back(static_cast<float>(dnrp::dev::cell_lds_bytes(a(3), a(4), 56 * a(2) / 4, wcap[0], wcap[1])));
+        } else if (n == "fused_lds_bytes") {  // (N_RX): the fused PDC receiver's LDS, one wave region per antenna
+            if (n_arg != 1 || a(0) == 0 || a(0) > 8) return DNRP_EINVAL;
+            v.push_back(static_cast<float>(dnrp::dev::rx_fused_lds(a(0))));
         } else if (n == "stf") {  // (b, N_eff_TX): transmit-stream vector [N_b_OCC + 1] re/im, scale 1
             if (n_arg != 2 || !(a(0) == 1 || a(0) == 2 || a(0) == 4 || a(0) == 8 || a(0) == 12 || a(0) == 16) ||
                 !(a(1) == 1 || a(1) == 2 || a(1) == 4 || a(1) == 8))

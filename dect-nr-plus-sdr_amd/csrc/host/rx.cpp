@@ -193,7 +193,8 @@ pdc_path choose_pdc_path(const switches& sw, const rx1_tables* t, const rx2_tabl
                          const dev::rx_cells_args& ca, uint32_t ng) {
     // both fused forms: the compile-time-tap wave front end and an instantiated (N_RX, N_eff_TX) pair
     const bool wave = fa.stream && dev::rx_fft_wave_path(fa);
-    if (sw.rx_fused && t2->fused_ok && fa.zd && wave && dev::rx_fused_supported(fa.N_RX, t->N_eff_TX))
+    if (sw.rx_fused && t2->fused_ok && fa.zd && wave && dev::rx_fused_supported(fa.N_RX, t->N_eff_TX) &&
+        dev::rx_fused_lds(fa.N_RX) <= 160 * 1024)
         return pdc_path::fused;
     if ((sw.rx_epoch >= 2 || (sw.rx_epoch == 1 && fa.N_RX >= 4)) && t2->ep_ok && !t2->sm && wave &&
         t2->bplan.cells_ok && t2->bplan.n_epochs && dev::rx_epoch_supported(fa.N_RX, t->N_eff_TX) &&

@@ -25,7 +25,209 @@ std::vector<float> window_rising(uint32_t N) {
     return rc;
 }
 
+// the window of a packet geometry at `fraction` (0: off): DNRP_OK with *win_n, or the error dnrp_tx_batch
+// returns before anything is queued -- the reference asserts 2 <= N (dft/windowing.cpp:39)
+int tx_window_n(const geo::dims_t& dm, const geo::resampler_t& rs, float fraction, uint32_t* win_n) {
+    *win_n = 0;
+    if (!(fraction > 0.0f)) return DNRP_OK;
+    const uint32_t N = window_length(dm.Nd, fraction);
+    if (N == 0) return dm.Nd % 8 ? DNRP_EUNSUPPORTED : DNRP_EINVAL;
+    // tx.hip tx_window_run leaves the prefix of a run's history symbol unshaped: the resampler
+    // history must end behind it
+    if (N > dm.CP || rs.hl + N >= dm.CP + dm.Nd) return DNRP_EUNSUPPORTED;
+    *win_n = N;
+    return DNRP_OK;
+}
+
+// what the launch geometry of a packet configuration is computed from: host data alone (a context's
+// tx_tables, or the geometry rebuilt without a device by dnrp_tx_form_for)
+struct tx_geom {
+    const dnrp_packet_sizes* q;
+    const geo::tm_t* tm;
+    const geo::dims_t* dm;
+    const geo::resampler_t* rs;
+    const uint32_t* pdc_off;   // [N_DF + 2] first PDC cell of each symbol
+    const uint8_t* w_onehot;   // per codebook: one nonzero entry in every antenna row
+    bool code_bin, code_oh;    // the streaming kernel's code tables exist (tables.cpp get_tx)
+};
+
+// Every value of the argument block that decides which kernel form launch_tx takes (dev::tx_form_of) and
+// with which launch geometry, for n packets of one configuration into iq_out at address out_addr with row
+// length S. Pure: no context, no device; the pointers of `a` stay unset.
+void plan_tx(const tx_geom& t, const switches& sw, uint32_t n, const dnrp_tx_desc* desc, uint32_t S, uint32_t pdc_stride,
+             uintptr_t out_addr, uint32_t win_n, dev::tx_args& a) {
+    const auto& q = *t.q;
+    const auto& tm = *t.tm;
+    const auto& dm = *t.dm;
+    const auto& rs = *t.rs;
+    a.plan.N = dm.Nd;
+    a.N_occ = q.N_b_OCC;
+    a.off_lower = dm.off_lower;
+    a.CP = dm.CP;
+    a.STF_CP = dm.STF_CP;
+    a.N_DF = q.N_DF_symb;
+    a.N_TS = tm.N_TS;
+    a.N_TX = tm.N_TX;
+    a.N_SS = tm.N_SS;
+    a.N_bps = q.N_bps;
+    a.txdiv = tm.txdiv;
+    fill_pairs(tm.N_TS, a.pair, a.mod);
+    a.pattern_len = dm.pattern_len;
+    a.L = rs.L;
+    a.M = rs.M;
+    a.delay = rs.delay;
+    a.hl = rs.hl;
+    a.n_keep = std::min(dm.N_no_GI_rs, S);
+    a.S = S;
+    a.pdc_stride = pdc_stride;
+    a.G = q.G;
+    a.win_n = win_n;
+    // symbol runs (tx.hip): K symbols per WG plus the preceding symbol as resampler history
+    // wave path (one wavefront per symbol slot): K = 6 symbols + history per 7-wave workgroup
+    // (C4, 4096 slots per launch: K=3 12.3 ms, K=4 16.6, K=5 15.2, K=6 11.4, K=7 15.9 — LDS sets
+    // 4 / 2 / 2 / 2 / 1 workgroups per CU); block path K = 3.
+    const bool wave = dm.Nd == 1024;
+    const uint32_t K = wave ? 6u : 3u;
+    a.K = K;
+    a.n_runs = (q.N_DF_symb + 1 + K - 1) / K;
+    const auto al = geo::resampler_align(rs);
+    a.m_star = al.m_star;
+    a.p_star = al.p_star;
+    a.HP = 2 * (rs.hl + rs.M + 1);
+    {
+        const uint32_t len0 = dm.STF_CP + dm.Nd, lenD = dm.CP + dm.Nd;
+        auto bsym = [&](uint32_t l) { return l == 0 ? 0u : len0 + (l - 1) * lenD; };
+        const uint32_t bpc = tm.N_SS * q.N_bps;
+        uint32_t mx = 0, span = 0;
+        for (uint32_t r = 0; r < a.n_runs; ++r) {
+            const uint32_t lf = r * K, ll = std::min(lf + K, q.N_DF_symb + 1) - 1, s0 = std::max(lf, 1u) - 1;
+            span = std::max(span, bsym(ll + 1) - bsym(s0));
+            const uint64_t b0 = (uint64_t(t.pdc_off[std::max(s0, 1u)]) * bpc) >> 3;
+            const uint64_t b1 = ((uint64_t(t.pdc_off[ll + 1]) * bpc + 7) >> 3) + 1;
+            if (b1 > b0) mx = std::max<uint32_t>(mx, static_cast<uint32_t>(b1 - b0));
+        }
+        a.stage_bytes = mx <= 8192 ? (mx + 3) / 4 * 4 : 0;
+        a.lin_len = std::max(2 * a.HP + span, (K + 1) * dm.Nd);
+        // output staging reuses bufB + twiddles + constellation: size bufB for the longest run
+        const uint32_t max_out = static_cast<uint32_t>((uint64_t(span + rs.hl) * rs.L + rs.M - 1) / rs.M) + rs.L;
+        a.bufB_len = std::max((K + 1) * dm.Nd, max_out > dm.Nd + 256 ? max_out - dm.Nd - 256 : 0u);
+    }
+    if (dm.Nd > 1024) {
+        // beyond the block path's registers (tx_kernel stages <= 4 bins per thread): the symbols go
+        // through a DECT-rate scratch (tx.hip tx_big_sym_kernel), e.g. u < u_max at b_max = 16
+        const uint64_t total = uint64_t(dm.STF_CP) + uint64_t(q.N_DF_symb) * dm.CP + uint64_t(q.N_DF_symb + 1) * dm.Nd;
+        a.big_len = static_cast<uint32_t>((total + 3) / 4 * 4);
+        // the scratch is capped at 4 GiB (sw.tx_big_cap): larger batches run in passes of big_batch packets (tx.hip)
+        const uint64_t row_bytes = sizeof(float) * 2 * uint64_t(a.big_len) * tm.N_TX;
+        a.big_batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(n, sw.tx_big_cap / row_bytes)));
+        a.stage_bytes = 0;
+    }
+    // streaming kernel (tx.hip tx_stream_kernel) where its geometry holds (its windowed form holds a
+    // window of up to CP = 128 samples)
+    a.stream = 0;
+    if (wave && t.code_bin && dev::tx_stream_taps_match(rs.h.data(), rs.h.size()) && a.L == 10 && a.M == 9 && a.hl == 22 && a.CP == 128 && a.STF_CP == 1280 &&
+        a.pattern_len * 9 == a.STF_CP + 1024 && S % 2 == 0 && (out_addr & 15u) == 0) {
+        // every symbol's PDC bytes (SFBC partners included) within its staging window: 1 KiB, spatial
+        // multiplexing 4 KiB (tx.hip TXS_SBW_SM: its first KiB prefetched, the rest loaded per symbol)
+        const uint32_t bpc = tm.N_SS * q.N_bps;
+        const bool sm = tm.N_TS > 1 && !tm.txdiv;
+        uint64_t span = 0;
+        for (uint32_t l = 1; l <= q.N_DF_symb; ++l) {
+            const uint64_t j0 = t.pdc_off[l] & ~1u, j1 = (uint64_t(t.pdc_off[l + 1]) + 1) & ~1ull;
+            const uint64_t ab = ((j0 * bpc) >> 3) & ~15ull, hi = ((j1 * bpc + 7) >> 3) + 1;
+            span = std::max(span, hi - ab);
+        }
+        const bool fits = span <= (sm ? 4096u : 1024u);
+        a.sb_chunks = static_cast<uint32_t>((span + 1023) / 1024);
+        const int qlo0 = -static_cast<int>((a.p_star + 8) / 9);
+        const int64_t mfirst0 = int64_t(a.m_star) + 10 * qlo0;
+        if (fits) {
+            a.stream = 1;
+            a.mfma = sw.tx_mfma;
+            a.onehot = tm.N_TS > 1 && t.code_oh ? 1u : 0u;  // transmit diversity or spatial multiplexing
+            for (uint32_t i = 0; i < n && a.onehot; ++i)
+                a.onehot = t.w_onehot[desc[i].codebook_index] ? 1u : 0u;
+            a.n_pieces = static_cast<uint32_t>((int64_t(a.n_keep) - mfirst0 + 1279) / 1280);
+            // enough wavefronts for ~8 rounds of 16 per CU; each extra segment costs one history FFT
+            const uint64_t per = uint64_t(n) * a.N_TX;
+            uint32_t ns = static_cast<uint32_t>(std::min<uint64_t>((32768 + per - 1) / per, std::max(1u, a.n_pieces / 8)));
+            a.n_seg = std::max(1u, ns);
+            a.piece_per_seg = (a.n_pieces + a.n_seg - 1) / a.n_seg;
+            a.n_seg = (a.n_pieces + a.piece_per_seg - 1) / a.piece_per_seg;
+        }
+    }
+}
+
+void export_form(const dev::tx_form& f, dnrp_tx_form* out) {
+    out->family = f.family;
+    out->L = f.L;
+    out->M = f.M;
+    out->hl = f.hl;
+    out->windowed = f.windowed;
+    out->mode = f.mode;
+    out->q8 = f.q8;
+    out->mfma = f.mfma;
+    out->sb_chunks = f.sb_chunks;
+    out->n_seg = f.n_seg;
+    out->staged = f.staged;
+    out->passes = f.passes;
+}
+
 }  // namespace
+
+extern "C" int dnrp_tx_last_form(const dnrp_ctx* ctx, dnrp_tx_form* out) {
+    if (!ctx || !out) return DNRP_EINVAL;
+    if (!ctx->tx_form_valid) return DNRP_ESTATE;
+    export_form(ctx->tx_form, out);
+    return DNRP_OK;
+}
+
+extern "C" int dnrp_tx_form_for(const dnrp_cfg* cfg, const dnrp_psdef* psdef, uint32_t n, const uint32_t* codebook, uint32_t S,
+                                uint32_t out_misalign, float win_fraction, dnrp_tx_form* out) {
+    if (!cfg || !psdef || !out || n == 0 || !codebook || !(win_fraction >= 0.0f && win_fraction <= 1.0f)) return DNRP_EINVAL;
+    dnrp_packet_sizes q{};
+    geo::tm_t tm{};
+    if (!geo::packet_sizes(*psdef, q, &tm)) return DNRP_ECONFIG;
+    if (psdef->u > cfg->u_max || psdef->b > cfg->b_max || q.N_TX > cfg->N_TX_max || q.N_bps > 8) return DNRP_EUNSUPPORTED;
+    const auto dm = geo::make_dims(*cfg, *psdef, q);
+    const auto rs = geo::make_resampler(cfg->L, cfg->M, cfg->os_min, prm::RS_TX);
+    if (S < dm.N_packet_rs) return DNRP_EINVAL;
+    if (q.N_b_OCC + 1 > 1024) return DNRP_EUNSUPPORTED;
+    uint32_t win_n = 0;
+    const int werr = tx_window_n(dm, rs, win_fraction, &win_n);
+    if (werr != DNRP_OK) return werr;
+    const auto m = geo::build_maps(psdef->b, tm.N_TS, tm.N_eff_TX, q.N_DF_symb);
+    const uint32_t ncb = geo::W_codebooks(tm.N_TS, tm.N_TX);
+    std::vector<uint8_t> onehot(ncb);
+    std::vector<dnrp_tx_desc> desc(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (codebook[i] >= ncb) return DNRP_EINVAL;
+        desc[i].codebook_index = codebook[i];
+    }
+    for (uint32_t cb = 0; cb < ncb; ++cb) {
+        float s = 1.0f;
+        const auto W = geo::W_matrix(tm.N_TS, tm.N_TX, cb, &s);
+        bool oh = true;
+        for (uint32_t a = 0; a < tm.N_TX; ++a) {
+            uint32_t nzc = 0;
+            for (uint32_t ts = 0; ts < tm.N_TS; ++ts) nzc += W[size_t(a) * tm.N_TS + ts] != std::complex<float>(0.f, 0.f) ? 1u : 0u;
+            oh = oh && nzc == 1;
+        }
+        onehot[cb] = oh ? 1 : 0;
+    }
+    // the streaming kernel's tables as tables.cpp get_tx builds them: the per-bin codes at 1024 points, the
+    // one-hot codes where every spatial stream's symbol index fits the code word
+    const uint64_t n_cells = m.pdc_sym_off.empty() ? 0 : m.pdc_sym_off.back();
+    const bool code_bin = dm.Nd == 1024;
+    const bool code_oh = code_bin && tm.N_TS > 1 && (tm.txdiv || n_cells == 0 || (n_cells - 1) * tm.N_SS + tm.N_TS - 1 <= dev::CODE_J_MASK);
+    switches sw;
+    read_tx(sw);
+    dev::tx_args a{};
+    plan_tx(tx_geom{&q, &tm, &dm, &rs, m.pdc_sym_off.data(), onehot.data(), code_bin, code_oh}, sw, n, desc.data(), S,
+            (q.G + 7) / 8, uintptr_t(out_misalign), win_n, a);
+    export_form(dev::tx_form_of(a, n), out);
+    return DNRP_OK;
+}
 
 extern "C" int dnrp_ctx_set_tx_windowing(dnrp_ctx* ctx, float fraction) {
     if (!ctx || !(fraction >= 0.0f && fraction <= 1.0f)) return DNRP_EINVAL;  // NaN fails both comparisons
@@ -59,12 +261,9 @@ extern "C" int dnrp_tx_batch(dnrp_ctx* ctx, const dnrp_psdef* psdef, uint32_t n,
     // queued -- the reference asserts 2 <= N (dft/windowing.cpp:39)
     uint32_t win_n = 0;
     const float* win = nullptr;
-    if (ctx->tx_win_fraction > 0.0f) {
-        win_n = window_length(t->dm.Nd, ctx->tx_win_fraction);
-        if (win_n == 0) return t->dm.Nd % 8 ? DNRP_EUNSUPPORTED : DNRP_EINVAL;
-        // tx.hip tx_window_run leaves the prefix of a run's history symbol unshaped: the resampler
-        // history must end behind it
-        if (win_n > t->dm.CP || t->rs.hl + win_n >= t->dm.CP + t->dm.Nd) return DNRP_EUNSUPPORTED;
+    err = tx_window_n(t->dm, t->rs, ctx->tx_win_fraction, &win_n);
+    if (err != DNRP_OK) return err;
+    if (win_n) {
         uint32_t fbits;
         std::memcpy(&fbits, &ctx->tx_win_fraction, sizeof fbits);
         auto& wb = ctx->tx_win[{t->dm.Nd, fbits}];
@@ -101,69 +300,16 @@ extern "C" int dnrp_tx_batch(dnrp_ctx* ctx, const dnrp_psdef* psdef, uint32_t n,
     HIPCHK(hipMemcpyAsync(ctx->tx_pk.p, pk, sizeof(dev::tx_pkt) * n, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(ctx->st_tx.ev, st));
     dev::tx_args a{};
+    plan_tx(tx_geom{&t->q, &t->tm, &t->dm, &t->rs, t->pdc_off_h.data(), t->w_onehot.data(), t->code_bin.p != nullptr,
+                    t->code_oh.p != nullptr},
+            ctx->sw, n, desc, S, pdc_stride, reinterpret_cast<uintptr_t>(iq_out), win_n, a);
     a.plan = t->plan;
-    a.N_occ = t->q.N_b_OCC;
-    a.off_lower = t->dm.off_lower;
-    a.CP = t->dm.CP;
-    a.STF_CP = t->dm.STF_CP;
-    a.N_DF = t->q.N_DF_symb;
-    a.N_TS = t->tm.N_TS;
-    a.N_TX = t->tm.N_TX;
-    a.N_SS = t->tm.N_SS;
-    a.N_bps = t->q.N_bps;
-    a.txdiv = t->tm.txdiv;
-    fill_pairs(t->tm.N_TS, a.pair, a.mod);
-    a.pattern_len = t->dm.pattern_len;
-    a.L = t->rs.L;
-    a.M = t->rs.M;
-    a.delay = t->rs.delay;
-    a.hl = t->rs.hl;
-    a.n_keep = std::min(t->dm.N_no_GI_rs, S);
-    a.S = S;
-    a.pdc_stride = pdc_stride;
-    a.G = t->q.G;
-    // symbol runs (tx.hip): K symbols per WG plus the preceding symbol as resampler history
-    // wave path (one wavefront per symbol slot): K = 6 symbols + history per 7-wave workgroup
-    // (C4, 4096 slots per launch: K=3 12.3 ms, K=4 16.6, K=5 15.2, K=6 11.4, K=7 15.9 — LDS sets
-    // 4 / 2 / 2 / 2 / 1 workgroups per CU); block path K = 3.
-    const bool wave = t->dm.Nd == 1024;
-    const uint32_t K = wave ? 6u : 3u;
-    a.K = K;
-    a.n_runs = (t->q.N_DF_symb + 1 + K - 1) / K;
-    const auto al = geo::resampler_align(t->rs);
-    a.m_star = al.m_star;
-    a.p_star = al.p_star;
-    a.HP = 2 * (t->rs.hl + t->rs.M + 1);
-    {
-        const uint32_t len0 = t->dm.STF_CP + t->dm.Nd, lenD = t->dm.CP + t->dm.Nd;
-        auto bsym = [&](uint32_t l) { return l == 0 ? 0u : len0 + (l - 1) * lenD; };
-        const uint32_t bpc = t->tm.N_SS * t->q.N_bps;
-        uint32_t mx = 0, span = 0;
-        for (uint32_t r = 0; r < a.n_runs; ++r) {
-            const uint32_t lf = r * K, ll = std::min(lf + K, t->q.N_DF_symb + 1) - 1, s0 = std::max(lf, 1u) - 1;
-            span = std::max(span, bsym(ll + 1) - bsym(s0));
-            const uint64_t b0 = (uint64_t(t->pdc_off_h[std::max(s0, 1u)]) * bpc) >> 3;
-            const uint64_t b1 = ((uint64_t(t->pdc_off_h[ll + 1]) * bpc + 7) >> 3) + 1;
-            if (b1 > b0) mx = std::max<uint32_t>(mx, static_cast<uint32_t>(b1 - b0));
-        }
-        a.stage_bytes = mx <= 8192 ? (mx + 3) / 4 * 4 : 0;
-        a.lin_len = std::max(2 * a.HP + span, (K + 1) * t->dm.Nd);
-        // output staging reuses bufB + twiddles + constellation: size bufB for the longest run
-        const uint32_t max_out = static_cast<uint32_t>((uint64_t(span + t->rs.hl) * t->rs.L + t->rs.M - 1) / t->rs.M) + t->rs.L;
-        a.bufB_len = std::max((K + 1) * t->dm.Nd, max_out > t->dm.Nd + 256 ? max_out - t->dm.Nd - 256 : 0u);
-    }
-    if (t->dm.Nd > 1024) {
-        // beyond the block path's registers (tx_kernel stages <= 4 bins per thread): the symbols go
-        // through a DECT-rate scratch (tx.hip tx_big_sym_kernel), e.g. u < u_max at b_max = 16
-        const uint64_t total = uint64_t(t->dm.STF_CP) + uint64_t(t->q.N_DF_symb) * t->dm.CP + uint64_t(t->q.N_DF_symb + 1) * t->dm.Nd;
-        a.big_len = static_cast<uint32_t>((total + 3) / 4 * 4);
-        // the scratch is capped at 4 GiB (sw.tx_big_cap): larger batches run in passes of big_batch packets (tx.hip)
+    if (a.big_len) {
+        // the DECT-rate scratch of the symbols (tx.hip tx_big_sym_kernel), big_batch packets per pass
         const uint64_t row_bytes = sizeof(float) * 2 * uint64_t(a.big_len) * t->tm.N_TX;
-        a.big_batch = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(n, ctx->sw.tx_big_cap / row_bytes)));
         if (!ctx->tx_big.ensure(row_bytes * a.big_batch)) return DNRP_ENOMEM;
         HIPCHK(ctx->tx_big.wait_idle(st));
         a.big = ctx->tx_big.as<float2>();
-        a.stage_bytes = 0;
     }
     a.code = t->code.as<uint32_t>();
     a.pdc_off = t->pdc_off.as<uint32_t>();
@@ -181,47 +327,16 @@ extern "C" int dnrp_tx_batch(dnrp_ctx* ctx, const dnrp_psdef* psdef, uint32_t n,
     a.out = iq_out;
     a.pk = ctx->tx_pk.as<dev::tx_pkt>();
     a.win = win;
-    a.win_n = win_n;
-    // streaming kernel (tx.hip tx_stream_kernel) where its geometry holds (its windowed form holds a
-    // window of up to CP = 128 samples)
-    a.stream = 0;
-    if (wave && t->code_bin.p && dev::tx_stream_taps_match(t->rs.h.data(), t->rs.h.size()) && a.L == 10 && a.M == 9 && a.hl == 22 && a.CP == 128 && a.STF_CP == 1280 &&
-        a.pattern_len * 9 == a.STF_CP + 1024 && S % 2 == 0 && (reinterpret_cast<uintptr_t>(iq_out) & 15u) == 0) {
-        // every symbol's PDC bytes (SFBC partners included) within its staging window: 1 KiB, spatial
-        // multiplexing 4 KiB (tx.hip TXS_SBW_SM: its first KiB prefetched, the rest loaded per symbol)
-        const uint32_t bpc = t->tm.N_SS * t->q.N_bps;
-        const bool sm = t->tm.N_TS > 1 && !t->tm.txdiv;
-        uint64_t span = 0;
-        for (uint32_t l = 1; l <= t->q.N_DF_symb; ++l) {
-            const uint64_t j0 = t->pdc_off_h[l] & ~1u, j1 = (uint64_t(t->pdc_off_h[l + 1]) + 1) & ~1ull;
-            const uint64_t ab = ((j0 * bpc) >> 3) & ~15ull, hi = ((j1 * bpc + 7) >> 3) + 1;
-            span = std::max(span, hi - ab);
-        }
-        const bool fits = span <= (sm ? 4096u : 1024u);
-        a.sb_chunks = static_cast<uint32_t>((span + 1023) / 1024);
-        const int qlo0 = -static_cast<int>((a.p_star + 8) / 9);
-        const int64_t mfirst0 = int64_t(a.m_star) + 10 * qlo0;
-        if (fits) {
-            a.stream = 1;
-            a.mfma = ctx->sw.tx_mfma;
-            a.code_bin = t->code_bin.as<uint32_t>();
-            a.onehot = t->tm.N_TS > 1 && t->code_oh.p ? 1u : 0u;  // transmit diversity or spatial multiplexing
-            for (uint32_t i = 0; i < n && a.onehot; ++i)
-                a.onehot = t->w_onehot[desc[i].codebook_index] ? 1u : 0u;
-            a.code_oh = t->code_oh.as<uint32_t>();
-            a.pcc_syms = t->pcc_syms;
-            a.n_pieces = static_cast<uint32_t>((int64_t(a.n_keep) - mfirst0 + 1279) / 1280);
-            // enough wavefronts for ~8 rounds of 16 per CU; each extra segment costs one history FFT
-            const uint64_t per = uint64_t(n) * a.N_TX;
-            uint32_t ns = static_cast<uint32_t>(std::min<uint64_t>((32768 + per - 1) / per, std::max(1u, a.n_pieces / 8)));
-            a.n_seg = std::max(1u, ns);
-            a.piece_per_seg = (a.n_pieces + a.n_seg - 1) / a.n_seg;
-            a.n_seg = (a.n_pieces + a.piece_per_seg - 1) / a.piece_per_seg;
-        }
+    if (a.stream) {
+        a.code_bin = t->code_bin.as<uint32_t>();
+        a.code_oh = t->code_oh.as<uint32_t>();
+        a.pcc_syms = t->pcc_syms;
     }
     ctx->tic("tx", st);
     if (dev::launch_tx(a, n, st) != hipSuccess) return DNRP_EDEVICE;
     ctx->toc("tx", st);
+    ctx->tx_form = dev::tx_form_of(a, n);  // dnrp_tx_last_form
+    ctx->tx_form_valid = true;
     HIPCHK(ctx->tx_pk.mark_busy(st));
     if (a.big) HIPCHK(ctx->tx_big.mark_busy(st));
     return DNRP_OK;

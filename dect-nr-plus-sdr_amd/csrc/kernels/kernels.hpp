@@ -82,6 +82,23 @@ struct tx_args {
     const float* win;
     uint32_t win_n;
 };
+// The kernel form launch_tx takes for an argument block: the one place where the choice is made
+// (tx_form_of, pure host code), read back through dnrp_tx_last_form.
+enum : uint32_t {
+    TXF_STREAM = 0,   // tx_stream_kernel<10, 9, 22, mode, q8, mfma, windowed>
+    TXF_WAVE = 1,     // tx_kernel_wave<L, M, hl, windowed> (N_b_DFT_os = 1024)
+    TXF_BLOCK = 2,    // tx_kernel<L, M, hl, windowed> (N_b_DFT_os < 1024)
+    TXF_SCRATCH = 3,  // tx_big_sym_kernel (+ tx_big_window_kernel) + tx_big_resample_kernel (N_b_DFT_os > 1024)
+};
+struct tx_form {
+    uint32_t family;     // TXF_*
+    uint32_t L, M, hl;   // resampler class compiled into the instantiation; 0, 0, 0: the run-time-ratio form
+    uint32_t windowed;
+    uint32_t mode, q8, mfma, sb_chunks, n_seg;  // stream: tx.hip TXS_* mode, 256-QAM form, matrix-core blocks, staging chunks, segments
+    uint32_t staged;     // wave, block: PDC bytes of a run staged in LDS (0: read from HBM)
+    uint32_t passes;     // scratch: passes of big_batch packets
+};
+tx_form tx_form_of(const tx_args& a, uint32_t n);
 hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st);
 bool tx_stream_taps_match(const float* h, size_t n);  // compiled-in 10/9 taps == run-time taps
 
@@ -297,6 +314,7 @@ struct rx_fused_args {
 };
 hipError_t launch_rx_fused(const rx_fused_args& a, hipStream_t st);
 bool rx_fused_supported(uint32_t N_RX, uint32_t NT);  // instantiated (N_RX, N_eff_TX) pairs
+size_t rx_fused_lds(uint32_t N_RX);                   // LDS bytes of a launch: one wave region per antenna
 
 struct rx_mimo_args {  // estimator_mimo_t::process_drs at the packet end, one wavefront per packet
     uint32_t N_RX, N_TS, Nf_pad, n_sym_total;

@@ -355,11 +355,14 @@ bool rx_fused_supported(uint32_t N_RX, uint32_t NT) {
     return (N_RX == 1 || N_RX == 2 || N_RX == 4 || N_RX == 8) && (NT == 1 || NT == 2 || NT == 4) && NT <= N_RX;
 }
 
+size_t rx_fused_lds(uint32_t N_RX) { return size_t(N_RX) * fused_region() * sizeof(float2); }
+
 hipError_t launch_rx_fused(const rx_fused_args& a, hipStream_t st) {
     if (!rx_fused_supported(a.F.N_RX, a.NT) || !rx_fft_wave_path(a.F) || !a.F.stream || !a.F.zd || a.n_fsym == 0)
         return hipErrorInvalidValue;
     const dim3 g((a.n_pkt + 7) / 8 * 8 * a.n_fsym), b(64 * a.F.N_RX);
-    const size_t lds = size_t(a.F.N_RX) * fused_region() * sizeof(float2);
+    const size_t lds = rx_fused_lds(a.F.N_RX);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
 #define DNRP_FUSED(R, T)                                                   \
     if (a.F.N_RX == R && a.NT == T) {                                      \
         hipLaunchKernelGGL((rx_fused_kernel<R, T>), g, b, lds, st, a);     \

@@ -1238,26 +1238,56 @@ size_t tx_lds_bytes(const tx_args& a) {
            a.npp * sizeof(float) + ((a.stage_bytes + 2 + 15) & ~15u);
 }
 
+tx_form tx_form_of(const tx_args& a, uint32_t n) {
+    tx_form f{};
+    f.windowed = a.win_n ? 1u : 0u;
+    if (a.stream) {
+        f.family = TXF_STREAM;
+        f.L = 10, f.M = 9, f.hl = 22;
+        f.mode = a.N_TS == 1 ? TXS_SISO : a.txdiv ? (a.onehot ? TXS_TXDIV1 : TXS_TXDIV) : (a.onehot ? TXS_SM1 : TXS_SM);
+        f.q8 = a.N_bps == 8 ? 1u : 0u;
+        f.mfma = a.mfma > 2 ? 1u : a.mfma;  // any other nonzero value takes the split-fp16 blocks
+        f.sb_chunks = a.sb_chunks;
+        f.n_seg = a.n_seg;
+        return f;
+    }
+    if (a.big_len) {
+        f.family = TXF_SCRATCH;
+        f.passes = a.big_batch ? (n + a.big_batch - 1) / a.big_batch : 0u;
+        return f;
+    }
+    f.family = a.plan.N == 1024 ? TXF_WAVE : TXF_BLOCK;
+    f.staged = a.stage_bytes ? 1u : 0u;
+    if (a.L == 10 && a.M == 9 && a.hl == 22)  // os_min 1 (223 taps)
+        f.L = 10, f.M = 9, f.hl = 22;
+    else if (a.L == 10 && a.M == 9 && a.hl == 4)  // os_min 2 (45 taps)
+        f.L = 10, f.M = 9, f.hl = 4;
+    else if (a.L == 1 && a.M == 1)
+        f.L = 1, f.M = 1, f.hl = 0;
+    return f;
+}
+
 hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st) {
     // windowing: a table of 2 <= win_n <= CP entries
     if (a.win_n && (!a.win || a.win_n < 2 || a.win_n > a.CP)) return hipErrorInvalidValue;
-    if (a.stream) {
+    const tx_form f = tx_form_of(a, n);
+    if (f.family == TXF_STREAM) {
         const uint64_t waves = uint64_t(n) * a.N_TX * a.n_seg;
         const dim3 g(static_cast<uint32_t>((waves + TXS_WPG - 1) / TXS_WPG)), b(64 * TXS_WPG);
-        const int mode = a.N_TS == 1 ? TXS_SISO : a.txdiv ? (a.onehot ? TXS_TXDIV1 : TXS_TXDIV) : (a.onehot ? TXS_SM1 : TXS_SM);
+        const uint32_t mode = f.mode;
         if (a.win_n > TXS_WIN) return hipErrorInvalidValue;
 #define DNRP_TXS_W(MODE, Q8, WIN)                                                                                           \
     do {                                                                                                                    \
-        if (a.mfma == 2) hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 2, WIN>), g, b, tx_stream_lds(WIN), st, a, n); \
-        else if (a.mfma) hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 1, WIN>), g, b, tx_stream_lds(WIN), st, a, n); \
+        if (f.mfma == 2) hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 2, WIN>), g, b, tx_stream_lds(WIN), st, a, n); \
+        else if (f.mfma) hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 1, WIN>), g, b, tx_stream_lds(WIN), st, a, n); \
         else hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 0, WIN>), g, b, tx_stream_lds(WIN), st, a, n);      \
     } while (0)
 #define DNRP_TXS(MODE, Q8)                          \
     do {                                            \
-        if (a.win_n) DNRP_TXS_W(MODE, Q8, true);    \
+        if (f.windowed) DNRP_TXS_W(MODE, Q8, true); \
         else DNRP_TXS_W(MODE, Q8, false);           \
     } while (0)
-        if (a.N_bps == 8) {
+        if (f.q8) {
             if (mode == TXS_SISO) DNRP_TXS(TXS_SISO, true);
             else if (mode == TXS_TXDIV) DNRP_TXS(TXS_TXDIV, true);
             else if (mode == TXS_TXDIV1) DNRP_TXS(TXS_TXDIV1, true);
@@ -1274,8 +1304,8 @@ hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st) {
 #undef DNRP_TXS_W
         return hipGetLastError();
     }
-    if (a.big) {
-        if (a.N_bps > 8 || a.stage_bytes || a.N_TS > 8) return hipErrorInvalidValue;
+    if (f.family == TXF_SCRATCH) {
+        if (!a.big || a.N_bps > 8 || a.stage_bytes || a.N_TS > 8) return hipErrorInvalidValue;
         const uint32_t total = a.STF_CP + a.N_DF * a.CP + (a.N_DF + 1) * a.plan.N;
         if (total > a.big_len) return hipErrorInvalidValue;
         const size_t lds = (2 * size_t(a.plan.N) + 256 + 98 + 8) * sizeof(float2);
@@ -1305,27 +1335,27 @@ hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st) {
         }
         return hipGetLastError();
     }
-    const bool wave = a.plan.N == 1024;
+    const bool wave = f.family == TXF_WAVE;
     if (a.K + 1 > TX_MAX_SLOTS || a.N_bps > 8) return hipErrorInvalidValue;
     if (!wave && (a.K + 1 > TX_BLOCK_SLOTS || a.plan.N > TX_BIN_REG * TX_THREADS)) return hipErrorInvalidValue;
     const size_t lds = tx_lds_bytes(a);
     const dim3 g(n * a.N_TX * a.n_runs), b(wave ? 64 * (a.K + 1) : TX_THREADS);
 #define DNRP_TX_LAUNCH(LR, MR, HLR)                                                      \
     do {                                                                                 \
-        if (wave && a.win_n)                                                             \
+        if (wave && f.windowed)                                                          \
             hipLaunchKernelGGL((tx_kernel_wave<LR, MR, HLR, true>), g, b, lds, st, a);   \
         else if (wave)                                                                   \
             hipLaunchKernelGGL((tx_kernel_wave<LR, MR, HLR, false>), g, b, lds, st, a);  \
-        else if (a.win_n)                                                                \
+        else if (f.windowed)                                                             \
             hipLaunchKernelGGL((tx_kernel<LR, MR, HLR, true>), g, b, lds, st, a);        \
         else                                                                             \
             hipLaunchKernelGGL((tx_kernel<LR, MR, HLR, false>), g, b, lds, st, a);       \
     } while (0)
-    if (a.L == 10 && a.M == 9 && a.hl == 22)  // os_min 1 (223 taps)
+    if (f.L == 10 && f.hl == 22)
         DNRP_TX_LAUNCH(10, 9, 22);
-    else if (a.L == 10 && a.M == 9 && a.hl == 4)  // os_min 2 (45 taps)
+    else if (f.L == 10 && f.hl == 4)
         DNRP_TX_LAUNCH(10, 9, 4);
-    else if (a.L == 1 && a.M == 1)
+    else if (f.L == 1)
         DNRP_TX_LAUNCH(1, 1, 0);
     else
         DNRP_TX_LAUNCH(0, 0, 0);

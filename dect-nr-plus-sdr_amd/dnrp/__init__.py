@@ -61,6 +61,22 @@ class TxDesc(C.Structure):
                 ("iq_phase_increment_s2s_post_resampling_rad", C.c_float), ("optimal_scaling_DAC", C.c_uint32)]
 
 
+TX_FORM_FIELDS = ["family", "L", "M", "hl", "windowed", "mode", "q8", "mfma", "sb_chunks", "n_seg", "staged", "passes"]
+TX_FORM_STREAM, TX_FORM_WAVE, TX_FORM_BLOCK, TX_FORM_SCRATCH = 0, 1, 2, 3
+TX_FAMILIES = ("stream", "wave", "block", "scratch")
+TXS_SISO, TXS_TXDIV, TXS_SM, TXS_TXDIV1, TXS_SM1 = 0, 1, 2, 3, 4  # dnrp_tx_form.mode of the stream family
+
+
+class TxForm(C.Structure):
+    """dnrp_tx_form: the kernel form of a dnrp_tx_batch (dnrp_tx_last_form, dnrp_tx_form_for)."""
+    _fields_ = [(n, C.c_uint32) for n in TX_FORM_FIELDS]
+
+    def as_dict(self):
+        d = {n: int(getattr(self, n)) for n in TX_FORM_FIELDS}
+        d["family"] = TX_FAMILIES[d["family"]]
+        return d
+
+
 class SyncReport(C.Structure):
     _fields_ = [("fine_peak_time", C.c_int64), ("cfo_fractional_rad", C.c_float), ("cfo_integer_rad", C.c_float),
                 ("u", C.c_uint32), ("b", C.c_uint32), ("N_eff_TX", C.c_uint32), ("window", C.c_uint32),
@@ -197,7 +213,8 @@ EXPORTS = ["dnrp_ctx_create", "dnrp_ctx_destroy", "dnrp_add_network_id", "dnrp_g
            "dnrp_pcc_decode_batch", "dnrp_pdc_decode_batch_harq", "dnrp_pdc_softbuffer_size",
            "dnrp_pcc_encode_batch", "dnrp_query_table", "dnrp_ctx_set_rx_mode", "dnrp_ctx_set_tx_windowing",
            "dnrp_tx_window", "dnrp_ctx_set_sync_beta_search", "dnrp_ctx_get_sync_beta_search",
-           "dnrp_ctx_set_sync_fine_all_antennas", "dnrp_ctx_get_sync_fine_all_antennas", "dnrp_rx_sync_fine_peaks"]
+           "dnrp_ctx_set_sync_fine_all_antennas", "dnrp_ctx_get_sync_fine_all_antennas", "dnrp_rx_sync_fine_peaks",
+           "dnrp_tx_last_form", "dnrp_tx_form_for"]
 
 _lib = None
 
@@ -226,6 +243,9 @@ def lib():
         L.dnrp_ctx_set_rx_mode.argtypes = [P, C.c_uint32]
         L.dnrp_ctx_set_tx_windowing.argtypes = [P, C.c_float]
         L.dnrp_tx_window.argtypes = [C.c_uint32, C.c_float, P, C.c_uint32]
+        L.dnrp_tx_last_form.argtypes = [P, C.POINTER(TxForm)]
+        L.dnrp_tx_form_for.argtypes = [C.POINTER(Cfg), C.POINTER(PsDef), C.c_uint32, P, C.c_uint32, C.c_uint32, C.c_float,
+                                       C.POINTER(TxForm)]
         L.dnrp_ctx_set_sync_beta_search.argtypes = [P, C.c_uint32, C.c_float]
         L.dnrp_ctx_get_sync_beta_search.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.dnrp_ctx_set_sync_fine_all_antennas.argtypes = [P, C.c_uint32]
@@ -290,6 +310,20 @@ def tx_window(N_b_DFT_os, fraction):
     out = np.zeros(n, np.float32)
     _chk(min(0, lib().dnrp_tx_window(int(N_b_DFT_os), float(fraction), C.c_void_p(out.ctypes.data), n)), "dnrp_tx_window")
     return out
+
+
+def tx_form_for(cfg, ps, codebooks, S=None, out_misalign=0, win_fraction=0.0):
+    """Host-only: the kernel form dnrp_tx_batch would take (dnrp_tx_form_for) as a dict. cfg: (u_max, b_max,
+    N_TX_max, os_min, L, M); codebooks: one index per packet; S: row length (default: the slot window)."""
+    u_max, b_max, ntx, os_min, L, M = cfg
+    c = Cfg(u_max, b_max, ntx, os_min, L, M, 1, 2, max(1, len(codebooks)), 0)
+    if S is None:
+        S = compute_packet_sizes(ps, u_max, b_max, os_min, L, M)["N_samples_packet_os_rs"]
+    cb = np.ascontiguousarray(np.asarray(codebooks, dtype=np.uint32))
+    out = TxForm()
+    _chk(lib().dnrp_tx_form_for(C.byref(c), C.byref(ps), len(cb), C.c_void_p(cb.ctypes.data), int(S), int(out_misalign),
+                                float(win_fraction), C.byref(out)), "dnrp_tx_form_for")
+    return out.as_dict()
 
 
 def query_table(name, *args):
@@ -440,6 +474,13 @@ class Phy:
         """dnrp_ctx_set_tx_windowing: raised-cosine symbol transitions (the reference's build option
         PHY_TX_OFDM_WINDOWING) for every later tx_batch; 0 turns them off (the default)."""
         _chk(lib().dnrp_ctx_set_tx_windowing(self._ctx, float(fraction)), "dnrp_ctx_set_tx_windowing")
+
+    def tx_last_form(self):
+        """dnrp_tx_last_form: the kernel form of the latest tx_batch as a dict (family "stream" / "wave" / "block" /
+        "scratch", resampler class, windowed, and the family's fields)."""
+        out = TxForm()
+        _chk(lib().dnrp_tx_last_form(self._ctx, C.byref(out)), "dnrp_tx_last_form")
+        return out.as_dict()
 
     def set_sync_beta_search(self, on, threshold_db=-10.0):
         """dnrp_ctx_set_sync_beta_search: every later rx_sync_batch / rx_sync_stream estimates the packet's

@@ -216,6 +216,44 @@ int dnrp_ctx_set_tx_windowing(dnrp_ctx* ctx, float fraction);
 int dnrp_tx_window(uint32_t N_b_DFT_os, float fraction, float* rising, uint32_t cap);
 
 /*
+ * The kernel form a dnrp_tx_batch launches, chosen from the packet geometry, the output buffer and the
+ * context's settings by one host function. dnrp_tx_batch has one timer ("tx"); this read-back is how a test
+ * proves which instantiation it ran.
+ *   family     DNRP_TX_FORM_STREAM: the streaming kernel (N_b_DFT_os = 1024 at 10/9, os_min 1, 9 STF patterns,
+ *              even S, iq_out 16-byte aligned, every symbol's PDC bytes inside its staging window);
+ *              DNRP_TX_FORM_WAVE: one wavefront per symbol, N_b_DFT_os = 1024 otherwise;
+ *              DNRP_TX_FORM_BLOCK: one workgroup per symbol run, N_b_DFT_os < 1024;
+ *              DNRP_TX_FORM_SCRATCH: symbols through a DECT-rate scratch, N_b_DFT_os > 1024
+ *   L, M, hl   resampler ratio and half length compiled into the instantiation: 10/9/22 (os_min 1), 10/9/4
+ *              (os_min 2), 1/1/0; 0/0/0: the form that takes them at run time (40/27, and the scratch family)
+ *   windowed   1 with dnrp_ctx_set_tx_windowing on
+ *   stream:    mode 0 SISO (N_TS = 1), 1 transmit diversity, 2 spatial multiplexing, 3 / 4 the same two where
+ *              every antenna row of every packet's W has one nonzero entry; q8: 256-QAM form; mfma: DNRP_TX_MFMA;
+ *              sb_chunks: KiB of a symbol's PDC byte window; n_seg: segments per antenna stream
+ *   wave, block: staged 1 where a symbol run's PDC bytes (<= 8192) are staged in LDS, 0 where they are read in place
+ *   scratch:   passes of the batch through the scratch (DNRP_TX_BIG_CAP)
+ * Fields of the other families are 0.
+ * dnrp_tx_last_form: the form of the context's latest dnrp_tx_batch that launched; DNRP_ESTATE before the first.
+ * dnrp_tx_form_for: host only, no context or device: the form dnrp_tx_batch would take for n packets of psdef
+ * with the codebook indices codebook[n], row length S, iq_out at an address congruent to out_misalign modulo
+ * 16, windowing fraction win_fraction (0: off), under the same environment switches. The errors are
+ * dnrp_tx_batch's for the same arguments.
+ */
+#define DNRP_TX_FORM_STREAM 0u
+#define DNRP_TX_FORM_WAVE 1u
+#define DNRP_TX_FORM_BLOCK 2u
+#define DNRP_TX_FORM_SCRATCH 3u
+typedef struct {
+    uint32_t family, L, M, hl, windowed;
+    uint32_t mode, q8, mfma, sb_chunks, n_seg;
+    uint32_t staged;
+    uint32_t passes;
+} dnrp_tx_form;
+int dnrp_tx_last_form(const dnrp_ctx* ctx, dnrp_tx_form* out);
+int dnrp_tx_form_for(const dnrp_cfg* cfg, const dnrp_psdef* psdef, uint32_t n, const uint32_t* codebook, uint32_t S,
+                     uint32_t out_misalign, float win_fraction, dnrp_tx_form* out);
+
+/*
  * Synchronisation: sync_chunk_t::search() on n windows, each window one chunk whose sync resampler
  * starts with zero history at sample 0 (reset_localbuffer, sync_chunk.cpp:300-311). Detection,
  * coarse peak and fine peak as in the reference; up to max_reports packets per window in search
@@ -557,6 +595,8 @@ const char* dnrp_param_name(uint32_t index);
  *   "stf_cover_sequence" ()      stf_t::cover_sequence (stf.hpp:146-151)
  *   "cells_lds_bytes" (u_max, b_max, b, N_RX, N_eff_TX)   LDS bytes of the PDC equaliser's staging for
  *                                the geometry; above 160 KiB dnrp_rx_*_batch return DNRP_EUNSUPPORTED
+ *   "fused_lds_bytes" (N_RX)     LDS bytes of a fused PDC receiver launch (DNRP_RX_FUSED=1); above 160 KiB the
+ *                                PDC phase takes another receiver
  *   "symbol_cells" (b, N_TS, N_eff_TX, N_DF)   per symbol l = 0..N_DF the number of PCC, PDC and DRS cells
  *   "pdc_cells" (b, N_TS, N_eff_TX, N_DF)   per PDC cell in mapping order: symbol l, subcarrier index k
  *                                (pdc.cpp:108-153; k counts from the lowest occupied subcarrier, DC included)

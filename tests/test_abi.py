@@ -62,6 +62,20 @@ def test_null_arguments():
     assert L.dnrp_tx_batch(None, None, 0, None, None, None, 0, None, 0, None) == -1
     assert L.dnrp_sync(None, None) == -1
     assert L.dnrp_rx_sync_batch(None, None, 0, None, 0, 0, 0, None, None, None) == -1
+    assert L.dnrp_tx_last_form(None, None) == -1
+    assert L.dnrp_tx_form_for(None, None, 0, None, 0, 0, 0.0, None) == -1
+
+
+def test_tx_form_layout_and_host_twin():
+    """dnrp_tx_form is 12 uint32 in the header's order, and dnrp_tx_form_for answers without a device: C3 takes the
+    streaming kernel's SISO 256-QAM form, C2 the block kernel with the 10/9 os_min 1 resampler."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = re.search(r"typedef struct \{([^}]*)\} dnrp_tx_form;", src).group(1)
+    assert re.findall(r"\b(\w+)\s*[,;]", body) == dnrp.TX_FORM_FIELDS and C.sizeof(dnrp.TxForm) == 48
+    c3 = dnrp.tx_form_for(F.CONFIGS["C3"][1], dnrp.psdef(*F.CONFIGS["C3"][0]), [0])
+    assert (c3["family"], c3["mode"], c3["q8"], c3["windowed"], c3["sb_chunks"]) == ("stream", dnrp.TXS_SISO, 1, 0, 1)
+    c2 = dnrp.tx_form_for(F.CONFIGS["C2"][1], dnrp.psdef(*F.CONFIGS["C2"][0]), [0], win_fraction=0.25)
+    assert (c2["family"], c2["L"], c2["M"], c2["hl"], c2["windowed"], c2["staged"]) == ("block", 10, 9, 22, 1, 1)
 
 
 def _grid():

@@ -22,6 +22,7 @@ import pytest
 import llr_gate
 import oracle_py as O
 import phy_fixtures as F
+import rx_grid_cases as RG
 
 torch = pytest.importorskip("torch")
 
@@ -41,18 +42,19 @@ def _ctx(name, max_batch=8, stride=2):
     return phy, dnrp.psdef(*ps), O.psdef(*ps), O.cfg(u_max, b_max, os_min, L, M, lr=lr, stride=stride)
 
 
-def _tx_inputs(rng, n, sz):
-    pcc = np.stack([O.pack_bits(F.random_bits(rng, 196)) for _ in range(n)])
-    pdc = np.stack([O.pack_bits(F.random_bits(rng, sz["G"])) for _ in range(n)])
-    assert pcc.shape == (n, 25) and pdc.shape == (n, (sz["G"] + 7) // 8)
-    return pcc, pdc
+_tx_inputs = RG.tx_inputs
 
 
-def _gpu_tx(phy, ps, descs, pcc, pdc, S):
+def _gpu_tx(phy, ps, descs, pcc, pdc, S, misalign=0):
+    """misalign: bytes (a multiple of 4) by which iq_out lies past a 16-byte boundary"""
     dev = torch.device("cuda:0")
     n = len(descs)
     sz = phy.packet_sizes(ps)
-    out = torch.empty((n, sz["N_TX"], S, 2), dtype=torch.float32, device=dev)
+    numel = n * sz["N_TX"] * S * 2
+    flat = torch.empty(numel + 4, dtype=torch.float32, device=dev)
+    assert flat.data_ptr() % 16 == 0 and misalign % 4 == 0 and misalign < 16
+    out = flat[misalign // 4: misalign // 4 + numel].view(n, sz["N_TX"], S, 2)
+    assert out.data_ptr() % 16 == misalign
     out.fill_(7.0)  # poison: every sample must be written
     phy.tx_batch(ps, descs, torch.from_numpy(pcc).to(dev), torch.from_numpy(pdc).to(dev), out)
     phy.sync()
@@ -73,6 +75,11 @@ def _check_tx(iq_gpu, ref, sz, S, n_tx_ref, tag):
 
 @pytest.mark.parametrize("name", sorted(TX_CASES))
 def test_tx_parity(name):
+    _tx_parity(name)
+
+
+def _tx_parity(name, misalign=0):
+    """One TX parity case of TX_CASES; returns the context (its dnrp_tx_last_form)."""
     import dnrp
     rng = np.random.default_rng(0xDEC7)
     phy, ps, ops, ocf = _ctx(name)
@@ -86,13 +93,14 @@ def test_tx_parity(name):
         cfo = (rng.uniform(-1.75, 1.75) * 2 * np.pi / sz["N_b_DFT_os"]) if i > 0 else 0.0
         descs.append(dnrp.TxDesc(cb, 100 + i, 1 + i % 2, 5, 1.0 if i != 1 else 0.7,
                                  float(rng.uniform(-3, 3)) if i == 2 else 0.0, cfo, 0))
-    iq = _gpu_tx(phy, ps, descs, pcc, pdc, S)
+    iq = _gpu_tx(phy, ps, descs, pcc, pdc, S, misalign)
     for i, d in enumerate(descs):
         ref, n_tx = O.tx(ocf, ops, pcc[i], pdc[i], S, codebook=cb, network_id=d.network_id,
                          plcf_type=d.plcf_type, gi=5, dac=float(np.float32(d.DAC_scale)),
                          phase=float(np.float32(d.iq_phase_rad)),
                          phase_inc=float(np.float32(d.iq_phase_increment_s2s_post_resampling_rad)))
         _check_tx(iq[i], ref, sz, S, n_tx, (name, i))
+    return phy
 
 
 @pytest.mark.parametrize("name", sorted(TX_CASES))
@@ -140,29 +148,9 @@ def test_tx_optimal_scaling_dac(name, cb):
 
 
 def _rx_windows(rng, name, phy, ps, ops, ocf, snrs, cb=0):
-    """Oracle-TX packets through a random N_RX x N_TX mixing, CFO and AWGN at per-packet SNRs.
-    Returns the windows, sync reports (with a small residual CFO error), network IDs, PLCF types
+    """tests/rx_grid_cases.py rx_windows for a context: the windows, sync reports, network IDs, PLCF types
     and the transmitted packed bits."""
-    import dnrp
-    sz = phy.packet_sizes(ps)
-    S = sz["N_samples_packet_os_rs"]
-    n_rx = phy.cfg.N_TX_max
-    n = len(snrs)
-    pcc, pdc = _tx_inputs(rng, n, sz)
-    windows, reports, nids, types = [], [], [], []
-    L, M = int(phy.cfg.L), int(phy.cfg.M)
-    for i in range(n):
-        nid, pt = 100 + (i % 6), 1 + i % 2
-        iq_tx, _ = O.tx(ocf, ops, pcc[i], pdc[i], S, codebook=cb, network_id=nid, plcf_type=pt)
-        off = int(rng.integers(0, 32))
-        cfo_dect = rng.uniform(-1.75, 1.75) * 2 * np.pi / sz["N_b_DFT_os"]  # rad per DECT sample
-        win = F.channel(rng, iq_tx, n_rx, S, off, cfo_dect * M / L, snrs[i])
-        windows.append(win)
-        est = -cfo_dect + rng.uniform(-0.02, 0.02) * 2 * np.pi / sz["N_b_DFT_os"]
-        reports.append(dnrp.SyncReport(off, float(est), 0.0, ops[0], ops[1], sz["N_eff_TX"]))
-        nids.append(nid)
-        types.append(pt)
-    return windows, reports, nids, types, pcc, pdc
+    return RG.rx_windows(rng, ops, ocf, phy.cfg.N_TX_max, snrs, cb)
 
 
 def _oracle_rx(ocf, ops, win, rep, nid, pt):
@@ -529,9 +517,13 @@ def test_rx_sm_mmse_parity(name):
     """GPU MMSE (rx_cells_kernel<., ., true>) vs the oracle's double-precision MMSE on the same windows:
     int16 LLRs within 1 LSB, SNR report within 0.05 dB; without the opt-in the PDC request is
     DNRP_EUNSUPPORTED, as the reference's receiver declines N_SS > 1."""
+    _rx_sm_parity(name, *SM_CASES[name])
+
+
+def _rx_sm_parity(name, ps_t, cf, snrs, prepared=None):
+    """prepared: (windows, reports, nids, types, pdc) built elsewhere instead of the case's own"""
     import dnrp
     rng = np.random.default_rng(17)
-    ps_t, cf, snrs = SM_CASES[name]
     u_max, b_max, ntx, os_min, L, M = cf
     phy = dnrp.Phy(u_max, b_max, ntx, os_min, L, M, max_batch=4)
     for nid in range(100, 106):
@@ -540,7 +532,10 @@ def test_rx_sm_mmse_parity(name):
     sz = phy.packet_sizes(ps)
     assert sz["N_SS"] > 1
     S = sz["N_samples_packet_os_rs"]
-    windows, reports, nids, types, _, pdc = _rx_windows(rng, name, phy, ps, ops, ocf, snrs)
+    if prepared is None:
+        windows, reports, nids, types, _, pdc = _rx_windows(rng, name, phy, ps, ops, ocf, snrs)
+    else:
+        windows, reports, nids, types, pdc = prepared
     n = len(windows)
     dev = torch.device("cuda:0")
     iq = torch.from_numpy(np.stack(windows).view(np.float32).reshape(n, ntx, S, 2)).to(dev)
@@ -564,6 +559,7 @@ def test_rx_sm_mmse_parity(name):
         if snrs[i] >= 30.0 and sz["N_bps"] <= 4:  # uncoded decisions; random flat H can be ill-conditioned
             bits = np.unpackbits(pdc[i])[: sz["G"]]
             assert np.mean(bits != (g_pdc[i] > 0)) < 5e-2, (name, i, np.mean(bits != (g_pdc[i] > 0)))
+    return phy
 
 
 def test_rx_tm10_unsupported():
