@@ -99,6 +99,11 @@ std::vector<float2> constellation(uint32_t N_bps);
 std::vector<float> taps_polyphase(const geo::resampler_t& rs, uint32_t* count);
 double phasor_arg(double rad);
 void fill_pairs(uint32_t N_TS, uint32_t* pair, uint32_t& mod);
+// the streaming TX kernel's code tables (tables.cpp; pure host code, dnrp_query_table "tx_code_oh")
+bool tx_pair_codes(std::vector<uint32_t>& code, uint32_t N_TS);  // false: a cell index past the code word
+std::vector<uint32_t> tx_code_bin(const std::vector<uint32_t>& code, uint32_t N_occ, uint32_t off_lower, uint32_t N_DF);
+std::vector<uint32_t> tx_code_oh(const std::vector<uint32_t>& cb, const uint32_t* pdc_off, uint32_t N_DF, uint32_t N_TS, uint32_t N_SS,
+                                 uint32_t N_bps, bool txdiv);
 
 struct tx_tables {
     dnrp_packet_sizes q{};

@@ -251,6 +251,29 @@ int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, floa
                 v.push_back(static_cast<float>(m.pdc_sym_off[l + 1] - m.pdc_sym_off[l]));
                 v.push_back(static_cast<float>(drs));
             }
+        } else if (n == "tx_code_oh") {  // (b, N_TS, N_eff_TX, N_DF, N_SS, N_bps, txdiv): the streaming TX kernel's
+            // one-hot code table at N_b_DFT_os = 1024 as get_tx uploads it, [N_TS][N_DF + 1][1024] words in the
+            // kernel's bin layout, per word its fields OH_BO, OH_SH, OH_WD, OH_K (kernels.hpp; the STF row: the
+            // CODE_* type, 0, 0, 0). Nothing where the table is not built.
+            if (n_arg != 7 || a(0) == 0 || a(0) > 16 || a(1) == 0 || a(1) > 8 || a(2) == 0 || a(2) > 8 || a(3) == 0 ||
+                a(3) > 1024 || a(4) == 0 || a(4) > 8 || a(5) == 0 || a(5) > 8)
+                return DNRP_EINVAL;
+            const auto m = geo::build_maps(a(0), a(1), a(2), a(3));
+            std::vector<uint32_t> code = m.code;
+            if (!host::tx_pair_codes(code, a(1))) return DNRP_EUNSUPPORTED;
+            const uint32_t N = 56 * a(0);
+            const auto cb = host::tx_code_bin(code, N, 1024 - N / 2, a(3));
+            const auto oh = host::tx_code_oh(cb, m.pdc_sym_off.data(), a(3), a(1), a(4), a(5), a(6) != 0);
+            for (size_t i = 0; i < oh.size(); ++i) {
+                const uint32_t c = oh[i];
+                if ((i / 1024) % (a(3) + 1) == 0) {
+                    for (const uint32_t x : {c >> 29, 0u, 0u, 0u}) v.push_back(static_cast<float>(x));
+                    continue;
+                }
+                for (const uint32_t x : {c & ((1u << dev::OH_BO_BITS) - 1u), (c >> dev::OH_SH_SHIFT) & 15u, (c >> dev::OH_WD_SHIFT) & 15u,
+                                         c >> dev::OH_K_SHIFT})
+                    v.push_back(static_cast<float>(x));
+            }
         } else if (n == "pdc_cells") {  // (b, N_TS, N_eff_TX, N_DF): per PDC cell in mapping order: symbol, subcarrier index
             if (n_arg != 4 || a(0) == 0 || a(0) > 16 || a(1) == 0 || a(1) > 8 || a(2) == 0 || a(2) > 8 || a(3) > 1024)
                 return DNRP_EINVAL;

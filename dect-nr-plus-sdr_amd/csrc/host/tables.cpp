@@ -75,6 +75,94 @@ bool mimo_codebook(uint32_t N, dbuf& W, dbuf& sc, uint32_t& ncb, uint32_t& A0) {
 
 namespace dnrp::host {
 
+bool tx_pair_codes(std::vector<uint32_t>& code, uint32_t N_TS) {
+    uint32_t pair[12], mod = 1;
+    fill_pairs(N_TS, pair, mod);
+    for (auto& c : code) {
+        const uint32_t ty = c & dev::CODE_MASK;
+        if (ty == dev::CODE_DRS) {  // DRS: the stream in the pair field too (one W-row read per bin)
+            c |= (c & 7u) << dev::CODE_PAIR_SHIFT;
+            continue;
+        }
+        if (ty != dev::CODE_PCC && ty != dev::CODE_PDC) continue;
+        const uint32_t j = c & ~dev::CODE_MASK;
+        if (j > dev::CODE_J_MASK) return false;
+        c = ty | j | (pair[(j >> 1) % mod] << dev::CODE_PAIR_SHIFT);
+    }
+    return true;
+}
+
+std::vector<uint32_t> tx_code_bin(const std::vector<uint32_t>& code, uint32_t N, uint32_t off_lower, uint32_t N_DF) {
+    const uint32_t Nf = N + 1;
+    std::vector<uint32_t> cb(size_t(N_DF + 1) * 1024, 0u);
+    for (uint32_t l = 0; l <= N_DF; ++l)
+        for (uint32_t nn = 0; nn < 1024; ++nn) {
+            uint32_t k = 0xFFFFFFFFu;
+            if (nn <= N / 2) k = N / 2 + nn;
+            else if (nn >= off_lower && nn < off_lower + N / 2) k = nn - off_lower;
+            // bin nn = lane + 64 m of the kernel's layout at [m / 4][lane][m % 4]: one 16-B load
+            // per lane fetches the codes of four of its bins
+            const uint32_t ln = nn & 63u, m = nn >> 6;
+            if (k != 0xFFFFFFFFu) cb[size_t(l) * 1024 + ((m >> 2) * 64 + ln) * 4 + (m & 3u)] = code[size_t(l) * Nf + k];
+        }
+    return cb;
+}
+
+// one-hot W rows: every bin's code resolved per antenna stream ts (tx.hip bin_oh, kernels.hpp OH_*):
+// the pair tests, the SFBC partner and its sign flips, the cell's place in the staged bytes and the
+// cell type itself become fields the kernel's two table reads take as they are (tx.hip bin_df
+// TXS_TXDIV1 / TXS_SM1 restated). Empty: not built (one stream, or a stream symbol index past the
+// code word of the pair-testing form, which dnrp_tx_form_for tests the same way).
+std::vector<uint32_t> tx_code_oh(const std::vector<uint32_t>& cb, const uint32_t* pdc_off, uint32_t N_DF, uint32_t N_TS, uint32_t N_SS,
+                                 uint32_t N_bps, bool txdiv) {
+    if (N_TS < 2 || N_bps == 0 || N_bps > 8) return {};
+    auto word = [](uint32_t bo, uint32_t sh, uint32_t wd, uint32_t k) {
+        return (bo & ((1u << dev::OH_BO_BITS) - 1u)) | (sh << dev::OH_SH_SHIFT) | (wd << dev::OH_WD_SHIFT) | (k << dev::OH_K_SHIFT);
+    };
+    // the index bit of a constellation point's re / im sign (36.211 7.1: the first / second bit; BPSK
+    // has one bit for both, its flipped points are slots of their own)
+    const uint32_t kx = N_bps == 1 ? dev::OH_Q_BPSK_FX : 1u << (N_bps - 1);
+    const uint32_t ky = N_bps == 1 ? dev::OH_Q_BPSK_FY : 1u << (N_bps - 2);
+    std::vector<uint32_t> oh(size_t(N_TS) * cb.size(), 0u);
+    for (uint32_t ts = 0; ts < N_TS; ++ts)
+        for (size_t i = 0; i < cb.size(); ++i) {
+            const uint32_t c = cb[i], ty = c & dev::CODE_MASK, j = c & dev::CODE_J_MASK;
+            const uint32_t pr = (c >> dev::CODE_PAIR_SHIFT) & 0xFFu, l = static_cast<uint32_t>(i / 1024);
+            const bool ua = (pr & 0xFu) == ts, ub = (pr >> 4) == ts;
+            if (l == 0) {  // the STF row: bin_stf reads the type alone
+                oh[size_t(ts) * cb.size() + i] = ty == dev::CODE_STF ? c : 0u;
+                continue;
+            }
+            uint32_t o = word(dev::OH_ZB, 8, 8, dev::OH_Q_ZERO);
+            // first staged byte of the symbol (tx.hip txs_wave::stage_base)
+            const uint64_t ab = ((uint64_t(pdc_off[l] & ~1u) * N_SS * N_bps) >> 3) & ~15ull;
+            auto pdc = [&](uint64_t js, uint32_t k) {  // PDC symbol js of the packet's stream
+                const uint64_t bit = js * N_bps - 8 * ab;
+                const uint32_t bo = static_cast<uint32_t>(std::min<uint64_t>(bit >> 3, dev::OH_ZB));  // in the window where the kernel runs (plan_tx)
+                return word(bo, 16 - static_cast<uint32_t>(bit & 7u) - N_bps, N_bps, k);
+            };
+            if (ty == dev::CODE_DRS) {
+                if (ua) o = word(dev::OH_ZB, 8, 8, dev::OH_Q_DRS + ((j & 8u) ? 1u : 0u));
+            } else if (ty == dev::CODE_PDC && !txdiv) {  // spatial multiplexing: the stream's symbol
+                const uint64_t js = uint64_t(j) * N_SS + ts;
+                if (js > dev::CODE_J_MASK) return {};
+                o = pdc(js, 0);
+            } else if ((ty == dev::CODE_PDC || ty == dev::CODE_PCC) && (ua || ub)) {
+                // SFBC: stream A maps symbol j, stream B the partner j ^ 1 with (-re, +im) for
+                // even j, (+re, -im) for odd j (transmit_diversity_precoding.cpp:37-75)
+                const uint32_t jp = j ^ (ua ? 0u : 1u);
+                if (ty == dev::CODE_PDC) {
+                    o = pdc(jp, ua ? 0u : ((j & 1u) ? ky : kx));
+                } else {  // QPSK of PCC bits 2 jp, 2 jp + 1 of the wave's descrambled bytes
+                    const uint32_t k = dev::OH_Q_QPSK ^ (ua ? 0u : ((j & 1u) ? 1u : 2u));
+                    o = word(dev::OH_PCB + ((2 * jp) >> 3), 14 - ((2 * jp) & 7u), 2, k);
+                }
+            }
+            oh[size_t(ts) * cb.size() + i] = o;
+        }
+    return oh;
+}
+
 tx_tables* get_tx(dnrp_ctx* ctx, const dnrp_psdef& d, int* err) {
     const auto key = std::make_tuple(d.u, d.b, d.PacketLengthType, d.PacketLength, d.tm_mode_index, d.mcs_index, d.Z);
     auto it = ctx->txt.find(key);
@@ -117,23 +205,9 @@ tx_tables* get_tx(dnrp_ctx* ctx, const dnrp_psdef& d, int* err) {
     t->pdc_off_h = m.pdc_sym_off;
     // transmit diversity TS pair (A | B << 4) per PCC/PDC cell into the code words (kernels.hpp CODE_*)
     std::vector<uint32_t> code = m.code;
-    {
-        uint32_t pair[12], mod = 1;
-        fill_pairs(t->tm.N_TS, pair, mod);
-        for (auto& c : code) {
-            const uint32_t ty = c & dev::CODE_MASK;
-            if (ty == dev::CODE_DRS) {  // DRS: the stream in the pair field too (one W-row read per bin)
-                c |= (c & 7u) << dev::CODE_PAIR_SHIFT;
-                continue;
-            }
-            if (ty != dev::CODE_PCC && ty != dev::CODE_PDC) continue;
-            const uint32_t j = c & ~dev::CODE_MASK;
-            if (j > dev::CODE_J_MASK) {
-                *err = DNRP_EUNSUPPORTED;
-                return nullptr;
-            }
-            c = ty | j | (pair[(j >> 1) % mod] << dev::CODE_PAIR_SHIFT);
-        }
+    if (!tx_pair_codes(code, t->tm.N_TS)) {
+        *err = DNRP_EUNSUPPORTED;
+        return nullptr;
     }
     if (uint64_t(t->dm.N_packet_rs + 2 * t->rs.hl) * t->rs.L >= (1ull << 32)) {  // 32-bit output indexing
         *err = DNRP_EUNSUPPORTED;
@@ -143,17 +217,7 @@ tx_tables* get_tx(dnrp_ctx* ctx, const dnrp_psdef& d, int* err) {
         // streaming TX kernel: cell code per FFT bin (tx.hip tx_wg::code layout, 0 for empty bins)
         const uint32_t N = t->q.N_b_OCC, Nf = N + 1, Nd = t->dm.Nd;
         if (Nd == 1024) {
-            std::vector<uint32_t> cb(size_t(t->q.N_DF_symb + 1) * 1024, 0u);
-            for (uint32_t l = 0; l <= t->q.N_DF_symb; ++l)
-                for (uint32_t nn = 0; nn < 1024; ++nn) {
-                    uint32_t k = 0xFFFFFFFFu;
-                    if (nn <= N / 2) k = N / 2 + nn;
-                    else if (nn >= t->dm.off_lower && nn < t->dm.off_lower + N / 2) k = nn - t->dm.off_lower;
-                    // bin nn = lane + 64 m of the kernel's layout at [m / 4][lane][m % 4]: one 16-B load
-                    // per lane fetches the codes of four of its bins
-                    const uint32_t ln = nn & 63u, m = nn >> 6;
-                    if (k != 0xFFFFFFFFu) cb[size_t(l) * 1024 + ((m >> 2) * 64 + ln) * 4 + (m & 3u)] = code[size_t(l) * Nf + k];
-                }
+            const std::vector<uint32_t> cb = tx_code_bin(code, N, t->dm.off_lower, t->q.N_DF_symb);
             for (uint32_t l = 0; l <= t->q.N_DF_symb; ++l)
                 for (uint32_t k = 0; k < Nf; ++k)
                     if ((code[size_t(l) * Nf + k] & dev::CODE_MASK) == dev::CODE_PCC) {
@@ -167,34 +231,8 @@ tx_tables* get_tx(dnrp_ctx* ctx, const dnrp_psdef& d, int* err) {
                 *err = DNRP_ENOMEM;
                 return nullptr;
             }
-            // one-hot W rows: every bin's code resolved per antenna stream ts (tx.hip bin_oh), so the
-            // kernel maps a bin without the pair tests (tx.hip bin_df TXS_TXDIV1 / TXS_SM1 restated)
-            const uint32_t NTS = t->tm.N_TS;
-            bool oh_ok = NTS > 1;
-            std::vector<uint32_t> oh(oh_ok ? size_t(NTS) * cb.size() : 0u, 0u);
-            for (uint32_t ts = 0; ts < NTS && oh_ok; ++ts)
-                for (size_t i = 0; i < cb.size(); ++i) {
-                    const uint32_t c = cb[i], ty = c & dev::CODE_MASK, j = c & dev::CODE_J_MASK;
-                    const uint32_t pr = (c >> dev::CODE_PAIR_SHIFT) & 0xFFu;
-                    const bool ua = (pr & 0xFu) == ts, ub = (pr >> 4) == ts;
-                    uint32_t o = 0;
-                    if (ty == dev::CODE_DRS) {
-                        if (ua) o = dev::CODE_DRS | ((j & 8u) ? dev::OH_FX : 0u);
-                    } else if (ty == dev::CODE_PDC && !t->tm.txdiv) {  // spatial multiplexing: the stream's symbol
-                        const uint64_t js = uint64_t(j) * t->tm.N_SS + ts;
-                        if (js > dev::CODE_J_MASK) oh_ok = false;
-                        o = dev::CODE_PDC | static_cast<uint32_t>(js & dev::CODE_J_MASK);
-                    } else if ((ty == dev::CODE_PDC || ty == dev::CODE_PCC) && (ua || ub)) {
-                        // SFBC: stream A maps symbol j, stream B the partner j ^ 1 with (-re, +im) for
-                        // even j, (+re, -im) for odd j (transmit_diversity_precoding.cpp:37-75)
-                        const uint32_t flip = ua ? 0u : ((j & 1u) ? dev::OH_FY : dev::OH_FX);
-                        o = ty | (j ^ (ua ? 0u : 1u)) | flip;
-                    } else if (ty == dev::CODE_STF) {
-                        o = c;
-                    }
-                    oh[size_t(ts) * cb.size() + i] = o;
-                }
-            if (oh_ok && !t->code_oh.upload(oh)) {
+            const std::vector<uint32_t> oh = tx_code_oh(cb, t->pdc_off_h.data(), t->q.N_DF_symb, t->tm.N_TS, t->tm.N_SS, t->q.N_bps, t->tm.txdiv);
+            if (!oh.empty() && !t->code_oh.upload(oh)) {
                 *err = DNRP_ENOMEM;
                 return nullptr;
             }

@@ -126,7 +126,7 @@ void plan_tx(const tx_geom& t, const switches& sw, uint32_t n, const dnrp_tx_des
     // window of up to CP = 128 samples)
     a.stream = 0;
     if (wave && t.code_bin && dev::tx_stream_taps_match(rs.h.data(), rs.h.size()) && a.L == 10 && a.M == 9 && a.hl == 22 && a.CP == 128 && a.STF_CP == 1280 &&
-        a.pattern_len * 9 == a.STF_CP + 1024 && S % 2 == 0 && (out_addr & 15u) == 0) {
+        a.pattern_len * 9 == a.STF_CP + 1024 && S % 2 == 0 && (out_addr & 15u) == 0 && q.G >= 121) {  // (a row of PDC bytes holds a 16-B load)
         // every symbol's PDC bytes (SFBC partners included) within its staging window: 1 KiB, spatial
         // multiplexing 4 KiB (tx.hip TXS_SBW_SM: its first KiB prefetched, the rest loaded per symbol)
         const uint32_t bpc = tm.N_SS * q.N_bps;

@@ -38,7 +38,8 @@ enum xs_bit : unsigned {
     // ---- measured alternatives (same results, slower)
     // wave FFT exchange slots XOR-swizzled instead of padded (conflict-free, +1-2 % TX)
     XS_WFFT_SWZ = 1u << 14,
-    // 256-QAM TX constellation from a separable 16-level table (two conflict-free reads, +3 % TX)
+    // 256-QAM TX constellation from a separable 16-level table (two conflict-free reads, +3 % TX); the
+    // pair-testing and single-stream forms only (the one-hot forms index the full table, kernels.hpp OH_*)
     XS_TX_QLEV = 1u << 15,
     // RX front end: the next symbol's span touched into L2 while this one is computed (+1.5 %)
     XS_FE_PREFETCH = 1u << 16,

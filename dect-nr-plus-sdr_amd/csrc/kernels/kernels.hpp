@@ -22,12 +22,29 @@ enum : uint32_t {
     CODE_STF = 4u << 29,
     CODE_MASK = 7u << 29,
     // one-hot W rows (tx.hip TXS_TXDIV1 / TXS_SM1): the code of a bin as seen by the antenna whose
-    // nonzero W entry is stream ts (host-built per ts, tables.cpp). Type PCC / PDC / DRS only where that
-    // stream carries the cell (else 0); bits 0..19: the symbol index to map (SFBC partner or spatial
-    // stream resolved), OH_FX / OH_FY: sign of its re / im part flipped (DRS: the point (1, 0), OH_FX
-    // for the value -1)
-    OH_FX = 1u << 20,
-    OH_FY = 1u << 21,
+    // nonzero W entry is stream ts (host-built per ts, tables.cpp tx_code_oh). The STF row (symbol 0)
+    // keeps the CODE_* words. A DF row holds what the kernel's table reads need, every cell type as
+    // data: the bin's value is W[ant][ts] * qtab[bits ^ OH_K], bits = OH_WD bits from bit OH_SH of the
+    // big-endian pair of bytes at OH_BO, OH_BO + 1 behind the symbol's first staged byte.
+    //   PDC cell: its symbol's bits in the staging window, OH_K the SFBC partner's sign flip as the
+    //     constellation index bit that carries that sign (re: the first bit, im: the second)
+    //   PCC cell: its two bits in the wave's descrambled PCC bytes (OH_PCB), OH_K the QPSK slots
+    //   DRS / empty cell: a zero byte (OH_ZB), OH_K the slot of (+-1, 0) / (0, 0)
+    // 256-QAM symbols without PCC cells read one byte: OH_BO and OH_K alone (OH_SH 8, OH_WD 8).
+    OH_BO_BITS = 15,
+    OH_SH_SHIFT = 15,  // 4 bits
+    OH_WD_SHIFT = 19,  // 4 bits
+    OH_K_SHIFT = 23,   // 9 bits, the word's top
+    // constellation slots behind the 256 of the PDC's table (tx.hip qtab)
+    OH_Q_DRS = 256,    // (1, 0), (-1, 0)
+    OH_Q_ZERO = 258,   // (0, 0)
+    OH_Q_QPSK = 260,   // the PCC's four points, index bits MSB first
+    OH_Q_BPSK_FX = 264,  // BPSK has no index bit per sign: its two points with re flipped,
+    OH_Q_BPSK_FY = 266,  // and with im flipped
+    OH_Q_SLOTS = 268,
+    // byte offsets from the symbol's first staged byte (tx.hip asserts them against its LDS layout)
+    OH_PCB = 9280,       // the wave's 32 descrambled PCC bytes, bytes 25..31 zero
+    OH_ZB = OH_PCB + 25,
 };
 
 // ---------------------------------------------------------------- TX

@@ -58,6 +58,14 @@ __device__ __forceinline__ uint32_t bits_of(uint32_t b0, uint32_t b1, uint32_t b
     return (w >> (16u - (bitoff & 7u) - nbits)) & ((1u << nbits) - 1u);
 }
 
+// a wave-uniform pointer into scalar registers (a descriptor built from it needs no waterfall loop)
+__device__ __forceinline__ const uint8_t* uniform_ptr(const uint8_t* p) {
+    const uintptr_t v = reinterpret_cast<uintptr_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
+    return reinterpret_cast<const uint8_t*>(uintptr_t(lo) | uintptr_t(hi) << 32);
+}
+
 __device__ __forceinline__ bool nz(float2 w) { return w.x != 0.f || w.y != 0.f; }
 
 __device__ __forceinline__ int floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
@@ -466,6 +474,10 @@ constexpr uint32_t TXS_BUF = TXS_CARRY + TXS_PIECE + 2;
 constexpr uint32_t TXS_XB = 32;                       // FFT exchange / PDC byte staging offset
 constexpr uint32_t TXS_WROW = 12;                     // beamforming row (8) + descrambled PCC bytes (32 B)
 static_assert(TXS_XB + WFFT_XB <= TXS_CARRY + TXS_PIECE, "FFT exchange buffer must fit behind the carry");
+constexpr uint32_t TXS_QT = OH_Q_SLOTS;               // constellation table slots ahead of the waves' buffers
+static_assert(TXS_QT % 2 == 0, "the waves' buffers stay 16-B aligned");
+// the one-hot code table's byte offsets (kernels.hpp): the PCC bytes sit behind the W row
+static_assert(OH_PCB == (TXS_BUF + 8 - TXS_XB) * 8, "OH_PCB is the PCC bytes' offset from the staged bytes");
 
 // TXS_TXDIV1: transmit diversity where every antenna's W row holds one nonzero entry (TM5 codebook 0:
 // W = I / 2): the antenna sends one stream of each SFBC pair, so a bin needs one PDC symbol and one
@@ -500,7 +512,7 @@ struct txs_wave {
     float2 w0;  // unscaled W[ant][0]: the STF bins carry scale_stf alone (tx.cpp:864-871)
     float2 wsel;  // TXS_TXDIV1: the antenna's one nonzero W entry, scale_df applied
     uint32_t tsel;  // TXS_TXDIV1: its stream
-    const uint8_t *dpdc, *cpdc;
+    const uint8_t *dpdc, *cpdc;  // the packet's d-bit row and its Gold sequence, pdc_bytes each (wave-uniform)
     uint32_t pdc_bytes;
 
     // first staged byte of symbol l (16-B aligned), PDC cells from pdc_off[l] & ~1 (SFBC partners)
@@ -509,24 +521,43 @@ struct txs_wave {
         const uint32_t j0 = reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(reinterpret_cast<uintptr_t>(A->pdc_off))[l] & ~1u;
         return ((j0 * A->N_SS * A->N_bps) >> 3) & ~15u;
     }
-    // 16-B chunk of the descrambled PDC bytes at byte g (zero beyond the packet) as the d-bit and
-    // Gold-sequence words, XORed where they are used: the loads are a prefetch, not waited for here
+    // 16-B chunk of the descrambled PDC bytes at byte g as the d-bit and Gold-sequence words, XORed where
+    // they are used (staged): the loads are a prefetch, not waited for here. The d-bit row sits behind
+    // a descriptor of its pdc_bytes (>= 16, launch_tx) bytes, so a chunk past the row's end reads zeros
+    // by the range check; the one chunk that straddles the end is read as the row's last 16 bytes, all
+    // in range, which staged() shifts into place -- no load reaches past a row's last byte, whatever the
+    // byte stride of the rows (the loads need no alignment). The Gold row (16-B aligned device memory)
+    // is read at the same offset, held inside the row; staged() drops what it read for a chunk past
+    // the end.
     __device__ void chunk(uint32_t g, uint4& d, uint4& c) const {
-        if (g + 16 <= pdc_bytes) {
-            // the d-bit rows need not be 16-B aligned (byte stride): one unaligned dwordx4 load
-            __builtin_memcpy(&d, dpdc + g, 16);
-            // the Gold row is 16-B aligned device memory: a global (not flat) load, so it retires in the
-            // vector-memory counter alone
-            typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-            const u4v cv = *reinterpret_cast<const __attribute__((address_space(1))) u4v*>(reinterpret_cast<uintptr_t>(cpdc + g));
-            c = make_uint4(cv.x, cv.y, cv.z, cv.w);
-            return;
+        const uint32_t last = pdc_bytes - 16u, off = g < pdc_bytes ? min(g, last) : g;
+        // (the descriptor is put together here, from the row pointer: scalar registers free over the piece loop)
+        const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(dpdc), 0, static_cast<int>(pdc_bytes), 0x00020000);
+        const mf_u4 dv = __builtin_amdgcn_raw_buffer_load_b128(drs, off, 0, 0);
+        d = make_uint4(dv.x, dv.y, dv.z, dv.w);
+        // a global (not flat) load, so it retires in the vector-memory counter alone
+        const mf_u4 cv = *reinterpret_cast<const __attribute__((address_space(1))) mf_u4*>(reinterpret_cast<uintptr_t>(cpdc + min(g, last)));
+        c = make_uint4(cv.x, cv.y, cv.z, cv.w);
+    }
+    // the staged word of the chunk at byte g0 + 16 lid (g0 wave-uniform, a multiple of 16): d ^ c; in the
+    // chunk that straddles the row's end moved down by the bytes its load started early (the same for
+    // every packet of the launch: 16 - pdc_bytes % 16) with zeros behind them, zero in a chunk past the
+    // end. Only a symbol whose 64 chunks reach the row's end pays for either (a scalar branch).
+    __device__ uint4 staged(uint4 d, uint4 c, uint32_t g0, uint32_t lid) const {
+        uint4 w = make_uint4(d.x ^ c.x, d.y ^ c.y, d.z ^ c.z, d.w ^ c.w);
+        if (g0 + 1024u > pdc_bytes) {
+            // (the shift per lane: as scalar selects its three conditions would be held over the piece loop)
+            uint32_t sft = (0u - pdc_bytes) & 15u;
+            asm volatile("" : "+v"(sft));
+            const uint32_t g = g0 + 16u * lid, a = sft >> 2, b = 8u * (sft & 3u);
+            const uint32_t u0 = a == 0 ? w.x : a == 1 ? w.y : a == 2 ? w.z : w.w, u1 = a == 0 ? w.y : a == 1 ? w.z : a == 2 ? w.w : 0u;
+            const uint32_t u2 = a == 0 ? w.z : a == 1 ? w.w : 0u, u3 = a == 0 ? w.w : 0u;
+            if (g + 16u > pdc_bytes)
+                w = make_uint4(__builtin_amdgcn_alignbit(u1, u0, b), __builtin_amdgcn_alignbit(u2, u1, b),
+                               __builtin_amdgcn_alignbit(u3, u2, b), __builtin_amdgcn_alignbit(0u, u3, b));
+            if (g >= pdc_bytes) w = make_uint4(0u, 0u, 0u, 0u);
         }
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-        for (uint32_t i = 0; i < 16; ++i)
-            if (g + i < pdc_bytes) w[i >> 2] |= uint32_t(dpdc[g + i] ^ cpdc[g + i]) << (8 * (i & 3));
-        d = make_uint4(w[0], w[1], w[2], w[3]);
-        c = make_uint4(0u, 0u, 0u, 0u);
+        return w;
     }
     // branch-free cell values: every source is read unconditionally at an in-bounds (masked)
     // index and the code type selects the result, so 16 bins per lane cost no divergent control
@@ -617,25 +648,21 @@ struct txs_wave {
         v = (ty == CODE_PDC || ty == CODE_DRS || (PCC && ty == CODE_PCC)) ? v : make_float2(0.f, 0.f);
         return v;  // wrow carries scale_df (one multiply per W entry instead of two per bin)
     }
-    // TXS_TXDIV1 / TXS_SM1 from the antenna stream's own code table (tables.cpp, kernels.hpp OH_*):
-    // the pair tests, the partner index and its flips were resolved on the host, so a bin is one
-    // table read, the flips as sign XORs and one complex product -- a DRS cell as the point (+-1, 0)
-    // (its sign an OH_FX flip), an empty cell as a zero W entry (bin_df's TXS_TXDIV1 branch, equal
-    // up to the sign of zero). Against the pair-testing form: TX 17.07 -> 16.66 ms per 16384 slots
-    template <bool Q8, bool PCC, uint32_t SBW>
-    __device__ float2 bin_oh(uint32_t c, const uint8_t* sb, uint32_t ab, const uint8_t* pcb) const {
+    // TXS_TXDIV1 / TXS_SM1 from the antenna stream's own code table (tables.cpp tx_code_oh, kernels.hpp
+    // OH_*): the pair tests, the partner index and its flips, the cell's place in the staged bytes
+    // and the cell type were resolved on the host, so a bin is one byte read (FAST: 256-QAM symbols
+    // without PCC cells; else two and a bit field), one read of the constellation table -- whose
+    // slots behind the PDC's hold the PCC's QPSK points, the DRS values (+-1, 0) and the (0, 0) of an
+    // empty cell; a partner's sign flip is the index bit that carries the sign -- and one complex
+    // product. Against the pair-testing form: TX 17.07 -> 16.66 ms per 16384 slots
+    template <bool FAST>
+    __device__ float2 bin_oh(uint32_t c, const uint8_t* sb) const {
         if constexpr (experiment(XS_TX_TRIVIAL_BINS)) return make_float2(__uint_as_float(c), 0.f);
-        const uint32_t ty = c & CODE_MASK, js = c & CODE_J_MASK;
-        float2 x = pdc_sym<Q8, SBW>(sb, ab, js);
-        if constexpr (PCC) {
-            const float2 px = pcc_sym(pcb, js);
-            x = ty == CODE_PCC ? px : x;
-        }
-        const bool kd = ty == CODE_DRS, kz = ty == 0u;
-        x = make_float2(kd ? 1.f : x.x, kd ? 0.f : x.y);
-        x = make_float2(__uint_as_float(__float_as_uint(x.x) ^ ((c << 11) & 0x80000000u)),
-                        __uint_as_float(__float_as_uint(x.y) ^ ((c << 10) & 0x80000000u)));
-        return cmul(make_float2(kz ? 0.f : wsel.x, kz ? 0.f : wsel.y), x);
+        const uint32_t bo = c & ((1u << OH_BO_BITS) - 1u), k = c >> OH_K_SHIFT;
+        uint32_t v = sb[bo];
+        if constexpr (!FAST) v = (((v << 8) | sb[bo + 1]) >> ((c >> OH_SH_SHIFT) & 15u)) & ((1u << ((c >> OH_WD_SHIFT) & 15u)) - 1u);
+        if constexpr (experiment(XS_TX_NO_QTAB)) return make_float2(static_cast<float>(v), -static_cast<float>(v));
+        return cmul(wsel, qtab[v ^ k]);
     }
     // STF bin n (stf.cpp:185-285 values, STF scaling)
     __device__ float2 bin_stf(uint32_t c, uint32_t n) const {
@@ -724,11 +751,14 @@ __global__ void __launch_bounds__(64 * TXS_WPG) __attribute__((amdgpu_waves_per_
     static_assert(PD::W == TXS_CARRY + 1, "carry = window - 1");
     static_assert(taps_tx_10_9::L == LR && taps_tx_10_9::M == MR && taps_tx_10_9::HL == HLR, "generated taps");
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
-    float2* qtab = smem;  // [256] per workgroup (256-QAM: the 16 levels in its first 8 slots)
+    // [TXS_QT] per workgroup: the PDC's constellation, behind it the slots of the one-hot code table
+    // (kernels.hpp OH_Q_*)
+    float2* qtab = smem;
+    constexpr bool OH = MODE == TXS_TXDIV1 || MODE == TXS_SM1;
     // wave index made provably uniform: everything derived from it (packet, segment, loop bounds,
     // pointers) stays in SGPRs and the piece loop is not divergent control flow
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    if constexpr (Q8 && experiment(XS_TX_QLEV)) {
+    if constexpr (Q8 && !OH && experiment(XS_TX_QLEV)) {
         // level i = re of the table entry whose I bits (0, 2, 4, 6) give index i and Q bits are 0
         if (threadIdx.x < 16) {
             const uint32_t i = threadIdx.x;
@@ -739,16 +769,30 @@ __global__ void __launch_bounds__(64 * TXS_WPG) __attribute__((amdgpu_waves_per_
         const uint32_t nq = 1u << A.N_bps;
         for (uint32_t i = threadIdx.x; i < nq; i += blockDim.x) qtab[i] = A.qam[i];
     }
+    if constexpr (OH) {
+        if (threadIdx.x < TXS_QT - 256) {
+            const uint32_t i = threadIdx.x;  // slot 256 + i
+            float2 e = make_float2(0.f, 0.f);
+            if (i < 2) e = make_float2(i ? -1.f : 1.f, 0.f);
+            // the PCC's QPSK points (TS 36.211 7.1.2), index bits MSB first
+            if (i >= OH_Q_QPSK - 256 && i < OH_Q_QPSK - 252) e = make_float2((i & 2u) ? -0.70710678f : 0.70710678f, (i & 1u) ? -0.70710678f : 0.70710678f);
+            if (i >= OH_Q_BPSK_FX - 256 && A.N_bps == 1) {  // BPSK point i & 1 with re (FX) or im (FY) flipped
+                const float2 p = A.qam[i & 1u];
+                e = i < OH_Q_BPSK_FY - 256 ? make_float2(-p.x, p.y) : make_float2(p.x, -p.y);
+            }
+            qtab[256 + i] = e;
+        }
+    }
     txs_wave T;
     T.A = &A;
     T.lane = lane;
     T.qtab = qtab;
     T.qlev = reinterpret_cast<float*>(qtab);
-    T.buf = smem + 256 + wv * (TXS_BUF + TXS_WROW);
+    T.buf = smem + TXS_QT + wv * (TXS_BUF + TXS_WROW);
     T.wrow = T.buf + TXS_BUF;
     txs_stash<WIN> ws;
     if constexpr (WIN) {
-        float* wtab = reinterpret_cast<float*>(smem + 256 + TXS_WPG * (TXS_BUF + TXS_WROW));  // [TXS_WIN]
+        float* wtab = reinterpret_cast<float*>(smem + TXS_QT + TXS_WPG * (TXS_BUF + TXS_WROW));  // [TXS_WIN]
         for (uint32_t i = threadIdx.x; i < TXS_WIN; i += blockDim.x) wtab[i] = i < A.win_n ? A.win[i] : 1.f;
         ws.tab = wtab;
         ws.s0 = ws.s1 = make_float2(0.f, 0.f);
@@ -776,9 +820,9 @@ __global__ void __launch_bounds__(64 * TXS_WPG) __attribute__((amdgpu_waves_per_
     if (!live) return;
     const uint32_t r_a = seg * A.piece_per_seg, r_b = min(r_a + A.piece_per_seg, A.n_pieces);
     if (r_a >= r_b) return;
-    T.dpdc = A.pdc_d + size_t(T.pkt) * A.pdc_stride;
-    T.cpdc = T.P.pdc_seq;
     T.pdc_bytes = (A.G + 7) / 8;
+    T.dpdc = uniform_ptr(A.pdc_d + size_t(T.pkt) * A.pdc_stride);
+    T.cpdc = uniform_ptr(T.P.pdc_seq);
     float2* buf = T.buf;
     float2* out = reinterpret_cast<float2*>(A.out) + size_t(T.pkt * A.N_TX + T.ant) * A.S;
     uint8_t* sb = reinterpret_cast<uint8_t*>(buf + TXS_XB);
@@ -830,7 +874,6 @@ __global__ void __launch_bounds__(64 * TXS_WPG) __attribute__((amdgpu_waves_per_
     // output stores, so waiting for them never waits for those stores (vmcnt retires in order)
     uint32_t cd[16];
     // one-hot W rows: the antenna stream's own code table (bin_oh)
-    constexpr bool OH = MODE == TXS_TXDIV1 || MODE == TXS_SM1;
     const uint32_t* ctab = OH ? A.code_oh + size_t(T.tsel) * (A.N_DF + 1) * 1024 : A.code_bin;
     auto load_codes = [&](uint32_t rr, uint32_t ln) {
         const uint32_t ls = txs_sym(rr, A.N_DF);
@@ -871,13 +914,13 @@ __global__ void __launch_bounds__(64 * TXS_WPG) __attribute__((amdgpu_waves_per_
         if (real) {
             // stage this symbol's bytes, prefetch the next symbol's
             const uint32_t ab = (l >= 1) ? T.stage_base(l) : 0u;
-            if (l >= 1) reinterpret_cast<uint4*>(sb)[lid] = make_uint4(pre.x ^ prc.x, pre.y ^ prc.y, pre.z ^ prc.z, pre.w ^ prc.w);
+            if (l >= 1) reinterpret_cast<uint4*>(sb)[lid] = T.staged(pre, prc, ab, lid);
             if constexpr (MODE == TXS_SM || MODE == TXS_SM1) {
                 if (l >= 1)
                     for (uint32_t c = 1; c < A.sb_chunks; ++c) {  // the window's other KiBs, not prefetched
                         uint4 d, e;
                         T.chunk(ab + 1024 * c + 16 * lid, d, e);
-                        reinterpret_cast<uint4*>(sb)[64 * c + lid] = make_uint4(d.x ^ e.x, d.y ^ e.y, d.z ^ e.z, d.w ^ e.w);
+                        reinterpret_cast<uint4*>(sb)[64 * c + lid] = T.staged(d, e, ab + 1024 * c, lid);
                     }
             }
             __builtin_amdgcn_wave_barrier();
@@ -887,7 +930,7 @@ __global__ void __launch_bounds__(64 * TXS_WPG) __attribute__((amdgpu_waves_per_
             } else if ((l < 32) && ((A.pcc_syms >> l) & 1u)) {
 #pragma unroll
                 for (int m = 0; m < 16; ++m) {
-                    if constexpr (OH) v[m] = T.template bin_oh<Q8, true, MODE == TXS_SM1 ? TXS_SBW_SM : 1024u>(cd[m], sb, ab, pcb);
+                    if constexpr (OH) v[m] = T.template bin_oh<false>(cd[m], sb);
                     else v[m] = T.template bin_df<MODE, Q8, true>(cd[m], sb, ab, pcb);
                 }
             } else {
@@ -895,7 +938,7 @@ __global__ void __launch_bounds__(64 * TXS_WPG) __attribute__((amdgpu_waves_per_
                 for (int m = 0; m < 16; ++m) {
                     // two groups of 8 bins: the table reads of 8 bins in flight at a time (all 16 spill)
                     if (OH && m == 8) __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (OH) v[m] = T.template bin_oh<Q8, false, MODE == TXS_SM1 ? TXS_SBW_SM : 1024u>(cd[m], sb, ab, pcb);
+                    if constexpr (OH) v[m] = T.template bin_oh<Q8>(cd[m], sb);
                     else v[m] = T.template bin_df<MODE, Q8, false>(cd[m], sb, ab, pcb);
                 }
             }
@@ -1085,7 +1128,8 @@ bool tx_stream_taps_match(const float* h, size_t n) {  // run-time taps == compi
 }
 
 size_t tx_stream_lds(bool win) {
-    return (256 + TXS_WPG * (TXS_BUF + TXS_WROW)) * sizeof(float2) + (win ? TXS_WIN * sizeof(float) : 0);
+    // 40,416 B (windowed 40,928): four workgroups per CU within the 160 KiB
+    return (TXS_QT + TXS_WPG * (TXS_BUF + TXS_WROW)) * sizeof(float2) + (win ? TXS_WIN * sizeof(float) : 0);
 }
 
 // ---- other FFT sizes: workgroup-wide batched Stockham FFT
@@ -1276,6 +1320,7 @@ hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st) {
         const dim3 g(static_cast<uint32_t>((waves + TXS_WPG - 1) / TXS_WPG)), b(64 * TXS_WPG);
         const uint32_t mode = f.mode;
         if (a.win_n > TXS_WIN) return hipErrorInvalidValue;
+        if (a.G < 121) return hipErrorInvalidValue;  // txs_wave::chunk: a row of PDC bytes holds a 16-B load
 #define DNRP_TXS_W(MODE, Q8, WIN)                                                                                           \
     do {                                                                                                                    \
         if (f.mfma == 2) hipLaunchKernelGGL((tx_stream_kernel<10, 9, 22, MODE, Q8, 2, WIN>), g, b, tx_stream_lds(WIN), st, a, n); \
