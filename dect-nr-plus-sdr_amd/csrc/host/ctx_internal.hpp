@@ -128,6 +128,9 @@ struct rx_plan_dev {
     dbuf dl, dmeta, segs, epochs;
     dbuf sym_op;  // [n_sym] first DRS op at symbol l, 0xFFFF: none (the front end's DRS test)
     uint32_t n_sym_op = 0;
+    // residual STO tracking: the ops' symbols on the host and as a front-end symbol list (launch_fft_list)
+    std::vector<uint32_t> dl_h;
+    dbuf dl16;
     bool upload(const geo::rx_plan_t& p) {
         static_assert(sizeof(geo::rx_seg_t) == sizeof(dev::rx_seg), "rx_seg layout");
         static_assert(sizeof(geo::rx_epoch_t) == sizeof(dev::rx_epoch), "rx_epoch layout");
@@ -142,7 +145,10 @@ struct rx_plan_dev {
         std::vector<uint16_t> so((lmax + 2) & ~1u, 0xFFFFu);  // whole dwords (scalar loads)
         for (uint32_t d = n_dops; d-- > 0;) so[p.dl[d]] = static_cast<uint16_t>(d);
         n_sym_op = lmax + 1;
-        return dl.upload(p.dl) && dmeta.upload(p.dmeta) && segs.upload(p.segs) && epochs.upload(p.epochs) && sym_op.upload(so);
+        dl_h = p.dl;
+        const std::vector<uint16_t> l16(p.dl.begin(), p.dl.end());
+        return dl.upload(p.dl) && dmeta.upload(p.dmeta) && segs.upload(p.segs) && epochs.upload(p.epochs) && sym_op.upload(so) &&
+               dl16.upload(l16);
     }
 };
 
@@ -322,6 +328,14 @@ struct dnrp_ctx {
     hipStream_t rx_aux = nullptr;
     hipEvent_t rx_fork = nullptr, rx_join = nullptr;
     uint32_t rx_mode = 0;  // DNRP_RX_MODE_* (dnrp_ctx_set_rx_mode)
+    // residual STO tracking from the DRS symbols (dnrp_ctx_set_rx_sto_tracking): the setting, and what the
+    // latest dnrp_rx_pcc_batch read of it (rx_sto_on / rx_sto_gain hold for that call's PDC call);
+    // sto_sym: [slot][rx_nsym_cap + 1] increment each symbol was derotated with, NaN where none was
+    uint32_t sto_track_on = 0;
+    float sto_track_gain = 1.0f;
+    bool rx_sto_on = false;
+    float rx_sto_gain = 1.0f;
+    dbuf sto_sym;
     pinned st_tx, st_rxin, st_seq, st_rep;
     // retained RX phase-1 state: per PCC-batch slot its (u, b, N_eff_TX) tables and symbol
     // capacity; Y is laid out with the batch-wide maxima rx_nsym_cap / rx_Nf_pad

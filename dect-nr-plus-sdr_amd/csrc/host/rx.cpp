@@ -189,38 +189,84 @@ enum class pdc_path {
 
 // every eligibility condition of the receivers, in order of preference. fa: the group's front-end
 // arguments (with the pilots zd where the front end writes them), ca: its cells arguments
+// sto_track: residual STO tracking is on (dnrp_ctx_set_rx_sto_tracking); the fused receiver and the grouped
+// Y path, the two measured-slower alternatives, do not take the per-symbol table and are never chosen then
 pdc_path choose_pdc_path(const switches& sw, const rx1_tables* t, const rx2_tables* t2, const dev::rx_front_args& fa,
-                         const dev::rx_cells_args& ca, uint32_t ng) {
+                         const dev::rx_cells_args& ca, uint32_t ng, bool sto_track) {
     // both fused forms: the compile-time-tap wave front end and an instantiated (N_RX, N_eff_TX) pair
     const bool wave = fa.stream && dev::rx_fft_wave_path(fa);
-    if (sw.rx_fused && t2->fused_ok && fa.zd && wave && dev::rx_fused_supported(fa.N_RX, t->N_eff_TX) &&
+    if (!sto_track && sw.rx_fused && t2->fused_ok && fa.zd && wave && dev::rx_fused_supported(fa.N_RX, t->N_eff_TX) &&
         dev::rx_fused_lds(fa.N_RX) <= 160 * 1024)
         return pdc_path::fused;
     if ((sw.rx_epoch >= 2 || (sw.rx_epoch == 1 && fa.N_RX >= 4)) && t2->ep_ok && !t2->sm && wave &&
         t2->bplan.cells_ok && t2->bplan.n_epochs && dev::rx_epoch_supported(fa.N_RX, t->N_eff_TX) &&
         dev::rx_epoch_lds(ca) <= 160 * 1024)
         return pdc_path::epoch;
-    if (sw.rx_group && ng > sw.rx_group && t2->q.N_DF_symb > t->pcc_max) return pdc_path::grouped_y;
+    if (!sto_track && sw.rx_group && ng > sw.rx_group && t2->q.N_DF_symb > t->pcc_max) return pdc_path::grouped_y;
     return pdc_path::plain_y;
 }
 
-// front end over a symbol list (the phase's DRS symbols) ahead of a fused receiver
-int launch_fft_list(dnrp_ctx* ctx, dev::rx_front_args fa, const dbuf& syms, uint32_t count, uint32_t n, hipStream_t st) {
+// front end over a symbol list (the phase's DRS symbols) ahead of a fused receiver, or ahead of
+// rx_sto_track_kernel. The wave front ends take the device list; rx_fft_kernel works on runs of
+// consecutive symbols, so it takes the host copy syms_h, one launch per symbol
+int launch_fft_list(dnrp_ctx* ctx, dev::rx_front_args fa, const uint16_t* syms, uint32_t count, uint32_t n, hipStream_t st,
+                    const uint32_t* syms_h = nullptr) {
     if (!count) return DNRP_OK;
-    fa.sym_first = 0;
-    fa.sym_list = syms.as<uint16_t>();
-    fa.sym_count = count;
+    const bool wave = dev::rx_fft_wave_path(fa);
+    if (!wave && !syms_h) return DNRP_EUNSUPPORTED;
     ctx->tic("rx_fft_pdc", st);
-    if (dev::launch_rx_fft(fa, n, st) != hipSuccess) return DNRP_EDEVICE;
+    for (uint32_t i = 0; i < (wave ? 1u : count); ++i) {
+        fa.sym_first = wave ? 0u : syms_h[i];
+        fa.sym_list = wave ? syms : nullptr;
+        fa.sym_count = wave ? count : 1u;
+        if (dev::launch_rx_fft(fa, n, st) != hipSuccess) return DNRP_EDEVICE;
+    }
     ctx->toc("rx_fft_pdc", st);
     return DNRP_OK;
+}
+
+// residual STO tracking of one phase (rx_sto_track_kernel): the phase's DRS rows are in Y, derotated with
+// the STF increment; fills the table entries of the symbols [sym_first, sym_last]
+int launch_sto_track(dnrp_ctx* ctx, const rx_phase& p, uint32_t sym_first, uint32_t sym_last, hipStream_t st) {
+    const rx1_tables* t = p.t;
+    dev::rx_sto_args a{};
+    a.N_RX = ctx->cfg.N_TX_max;
+    a.Nf_pad = ctx->rx_Nf_pad;
+    a.n_sym_total = ctx->rx_nsym_cap + 1;
+    a.n_drs = t->N_occ / 4;
+    a.n_dops = p.plan->n_dops;
+    a.N_occ = t->N_occ;
+    a.is_pdc = p.pdc;
+    a.sym_first = sym_first;
+    a.sym_last = sym_last;
+    a.gain = ctx->rx_sto_gain;
+    a.dl = p.plan->dl.as<uint32_t>();
+    a.dmeta = p.plan->dmeta.as<uint32_t>();
+    a.drs_k = t->drs_k.as<uint32_t>();
+    a.drs_v = t->drs_v.as<float>();
+    a.Y = ctx->Y.as<float2>();
+    a.st = ctx->rx_st.as<dev::rx_pkt_state>();
+    a.sel = p.sel;
+    a.tab = ctx->sto_sym.as<double>();
+    ctx->tic("rx_sto_track", st);
+    if (dev::launch_rx_sto_track(a, p.n, st) != hipSuccess) return DNRP_EDEVICE;
+    ctx->toc("rx_sto_track", st);
+    return DNRP_OK;
+}
+
+// the PDC phase's part of residual STO tracking on the Y rows a DRS pass with the STF increment left; fa
+// then carries the table for the phase's launches
+int pdc_sto_track(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_front_args& fa, hipStream_t st) {
+    const int err = launch_sto_track(ctx, p, p.t->pcc_max + 1, t2->q.N_DF_symb, st);
+    fa.sto_sym = ctx->sto_sym.as<double>();
+    return err;
 }
 
 // the phase's DRS symbols first (pilots, SNR sums; their bins to Y only where they carry PDC cells),
 // then the SNR chain / LUT picks, then one fused launch for every PDC symbol
 int pdc_fused(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_front_args fa, hipStream_t st) {
     fa.no_y = t2->drs_y ? 0u : 1u;
-    int err = launch_fft_list(ctx, fa, t2->drs_syms, t2->n_drs_syms, p.n, st);
+    int err = launch_fft_list(ctx, fa, t2->drs_syms.as<uint16_t>(), t2->n_drs_syms, p.n, st);
     if (err == DNRP_OK) err = launch_snr_chain(ctx, p, st);
     if (err != DNRP_OK) return err;
     dev::rx_fused_args x{};
@@ -247,10 +293,15 @@ int pdc_fused(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_fr
 
 // DRS pass (the phase's DRS symbols: pilots in Y, SNR sums), the SNR chain's LUT picks, then one
 // workgroup per (packet, epoch): front end of the epoch's symbols + equaliser, on the twin plan where
-// the phase has one
-int pdc_epoch(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const dev::rx_front_args& fa,
+// the phase has one. With residual STO tracking the DRS pass feeds rx_sto_track_kernel and is repeated
+// with its table, which the epoch kernel's front end takes too
+int pdc_epoch(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_front_args fa,
               const dev::rx_cells_args& ca, hipStream_t st) {
-    int err = launch_fft_list(ctx, fa, t2->ep_drs, t2->n_ep_drs, p.n, st);
+    int err = launch_fft_list(ctx, fa, t2->ep_drs.as<uint16_t>(), t2->n_ep_drs, p.n, st);
+    if (err == DNRP_OK && ctx->rx_sto_on) {
+        err = pdc_sto_track(ctx, p, t2, fa, st);
+        if (err == DNRP_OK) err = launch_fft_list(ctx, fa, t2->ep_drs.as<uint16_t>(), t2->n_ep_drs, p.n, st);
+    }
     if (err == DNRP_OK) err = launch_snr_chain(ctx, p, st);
     if (err != DNRP_OK) return err;
     dev::rx_epoch_args x{};
@@ -306,6 +357,12 @@ int pdc_grouped_y(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::r
 int pdc_plain_y(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_front_args fa,
                 const dev::rx_cells_args& ca, hipStream_t st) {
     if (t2->q.N_DF_symb > p.t->pcc_max) {
+        if (ctx->rx_sto_on) {  // the phase's DRS symbols (the plan's ops behind the PCC phase's) first
+            const uint32_t d0 = p.t->bplan.n_dops, nd = p.plan->n_dops - d0;
+            int err = launch_fft_list(ctx, fa, p.plan->dl16.as<uint16_t>() + d0, nd, p.n, st, p.plan->dl_h.data() + d0);
+            if (err == DNRP_OK) err = pdc_sto_track(ctx, p, t2, fa, st);
+            if (err != DNRP_OK) return err;
+        }
         fa.sym_count = t2->q.N_DF_symb - p.t->pcc_max;
         ctx->tic("rx_fft_pdc", st);
         if (dev::launch_rx_fft(fa, p.n, st) != hipSuccess) return DNRP_EDEVICE;
@@ -349,7 +406,12 @@ int pdc_mimo(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const dev::
 int pdc_group(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const float* iq_in, bool mimo, hipStream_t st) {
     auto fa = front_args(ctx, p.t, iq_in, p.sel, snr_from_front(ctx, p.t) ? p.plan : nullptr);
     const auto ca = cells_args(ctx, p);
-    const pdc_path path = choose_pdc_path(ctx->sw, p.t, t2, fa, ca, p.n);
+    const pdc_path path = choose_pdc_path(ctx->sw, p.t, t2, fa, ca, p.n, ctx->rx_sto_on);
+    if (ctx->rx_sto_on) {  // the PCC plan's ops are the PDC plan's ops up to pcc_max: the state continues there
+        uint32_t d0 = 0;
+        while (d0 < p.plan->n_dops && p.plan->dl_h[d0] <= p.t->pcc_max) ++d0;
+        if (d0 != p.t->bplan.n_dops) return DNRP_EUNSUPPORTED;
+    }
     if (path != pdc_path::fused) {
         fa.zd = nullptr;  // no reader
         fa.sym_first = p.t->pcc_max + 1;
@@ -440,6 +502,13 @@ int dnrp_rx_pcc_batch(dnrp_ctx* ctx, uint32_t n, const dnrp_sync_report* sr, con
         !ctx->nv_d.ensure(size_t(ctx->cfg.max_batch) * dev::RX_MAX_DOPS * sizeof(float)))
         return DNRP_ENOMEM;
     read_pcc(ctx->sw);  // once per PCC call: its PDC call takes the same switches
+    ctx->rx_sto_on = ctx->sto_track_on != 0;  // likewise the residual STO tracking setting
+    ctx->rx_sto_gain = ctx->sto_track_gain;
+    if (ctx->rx_sto_on) {  // the per-symbol table, NaN (all bits set) until a phase fills its symbols
+        const size_t tbytes = size_t(n) * (ctx->rx_nsym_cap + 1) * sizeof(double);
+        if (!ctx->sto_sym.ensure(tbytes)) return DNRP_ENOMEM;
+        HIPCHK(hipMemsetAsync(ctx->sto_sym.p, 0xFF, tbytes, st));
+    }
     {
         // zero-forced DRS pilots of every slot (the fused receiver's only): at most one DRS symbol per
         // 5 symbols (N_eff_TX <= 4) plus the zero op
@@ -490,10 +559,18 @@ int dnrp_rx_pcc_batch(dnrp_ctx* ctx, uint32_t n, const dnrp_sync_report* sr, con
         ctx->toc("rx_stf", st);
         fa.sym_first = 1;
         fa.sym_count = t->pcc_max;
-        ctx->tic("rx_fft_pcc", st);
-        if (dev::launch_rx_fft(fa, ng, st) != hipSuccess) return DNRP_EDEVICE;
-        ctx->toc("rx_fft_pcc", st);
         const rx_phase p{t, &t->bplan, ng, gsel, false, 2, t->pcc_k.as<uint32_t>(), t->pcc_sym.as<uint16_t>(), pcc_llr, 196, false};
+        // residual STO tracking: the phase's few symbols with the STF increment, the table from their DRS
+        // rows, then the same launch again with the table
+        for (int pass = ctx->rx_sto_on ? 0 : 1; pass < 2; ++pass) {
+            ctx->tic("rx_fft_pcc", st);
+            if (dev::launch_rx_fft(fa, ng, st) != hipSuccess) return DNRP_EDEVICE;
+            ctx->toc("rx_fft_pcc", st);
+            if (pass) break;
+            err = launch_sto_track(ctx, p, 0, t->pcc_max, st);
+            if (err != DNRP_OK) return err;
+            fa.sto_sym = ctx->sto_sym.as<double>();
+        }
         const auto ca = cells_args(ctx, p);
         err = launch_back(ctx, p, &ca, st);
         if (err != DNRP_OK) return err;
@@ -556,6 +633,7 @@ int dnrp_rx_pdc_batch(dnrp_ctx* ctx, uint32_t m, const dnrp_pdc_req* req, const 
         rx2_tables* t2 = get_rx2(ctx, d, &err);
         if (!t2) return err;
         if (d.u != t->u || d.b != t->b || t2->q.N_eff_TX != t->N_eff_TX) return DNRP_EINVAL;
+        if (ctx->rx_sto_on && t2->sm) return DNRP_EUNSUPPORTED;  // the MMSE receiver has no tracking; nothing launched yet
         if (llr_stride < t2->q.G) return DNRP_EINVAL;
         for (uint32_t r : g.second) {
             if (t2->q.N_DF_symb > ctx->rx_slot_cap[req[r].pcc_index]) return DNRP_EINVAL;
@@ -589,6 +667,31 @@ int dnrp_rx_pdc_batch(dnrp_ctx* ctx, uint32_t m, const dnrp_pdc_req* req, const 
         if (err != DNRP_OK) return err;
     }
     return rep ? pdc_reports(ctx, m, req, rep, st) : DNRP_OK;
+}
+
+int dnrp_ctx_set_rx_sto_tracking(dnrp_ctx* ctx, uint32_t on, float gain) {
+    if (!ctx || on > 1 || !std::isfinite(gain) || gain < 0.0f || gain > 1.0f) return DNRP_EINVAL;
+    ctx->sto_track_on = on;
+    ctx->sto_track_gain = gain;
+    return DNRP_OK;
+}
+
+int dnrp_ctx_get_rx_sto_tracking(const dnrp_ctx* ctx, uint32_t* on, float* gain) {
+    if (!ctx) return DNRP_EINVAL;
+    if (on) *on = ctx->sto_track_on;
+    if (gain) *gain = ctx->sto_track_gain;
+    return DNRP_OK;
+}
+
+int dnrp_rx_sto_track(dnrp_ctx* ctx, uint32_t n_slots, double* inc, uint32_t n_sym_cap, uint32_t* n_sym, void* stream) {
+    if (!ctx || !n_sym || !ctx->rx_valid || !ctx->rx_sto_on) return DNRP_EINVAL;
+    *n_sym = ctx->rx_nsym_cap + 1;
+    if (!inc) return DNRP_OK;  // size query
+    if (n_slots == 0 || n_slots > ctx->rx_n || n_sym_cap < *n_sym) return DNRP_EINVAL;
+    (void)hipSetDevice(ctx->cfg.device);
+    HIPCHK(hipMemcpyAsync(inc, ctx->sto_sym.p, size_t(n_slots) * *n_sym * sizeof(double), hipMemcpyDeviceToHost,
+                          static_cast<hipStream_t>(stream)));
+    return DNRP_OK;
 }
 
 }  // extern "C"

@@ -135,6 +135,10 @@ struct rx_pkt_state {       // written by rx_stf_kernel, read by the later RX ke
     float cfo_fine, sto_frac;
     float rms[8];
     float snr_pcc, snr_pdc;
+    // residual STO tracking (rx_sto_track_kernel): the running increment after the PCC phase's DRS ops and
+    // the number of those ops, where the PDC phase continues; rx_stf_kernel starts them at (sto_inc, 0)
+    double sto_run;
+    uint32_t sto_ops, pad0;
 };
 
 struct rx_front_args {
@@ -186,6 +190,9 @@ struct rx_front_args {
     uint32_t stf_chunk;             // rx_stf_ant_kernel: 0, or outputs per resampling chunk (launch_rx_stf)
     uint32_t y_plain;               // 1: Y stored with plain (cache-allocating) stores, re-read from the
                                     // caches by the next packet group's back end; 0: nontemporal stores
+    // residual STO tracking (rx_sto_track_kernel's table): symbol l of a slot is derotated with
+    // sto_sym[slot n_sym_total + l] instead of the packet's rx_pkt_state::sto_inc; null: sto_inc
+    const double* sto_sym;
 };
 bool rx_fft_wave_path(const rx_front_args& a);  // launch_rx_fft takes rx_fft_wave_kernel (snr_part supported)
 hipError_t launch_rx_stf(const rx_front_args& a, uint32_t n, hipStream_t st);
@@ -224,6 +231,24 @@ struct rx_snr_args {        // DRS zero-forcing SNR chain + LUT profile picks, o
     const double2* snr_part;  // front-end partial sums (rx_front_args::snr_part) or null: gather from Y
 };
 hipError_t launch_rx_snr(const rx_snr_args& a, uint32_t n, hipStream_t st);
+
+// Residual STO from the DRS symbols (estimator_sto.cpp:64-97, 148-171), one WG per packet: the phase
+// plan's DRS ops in order, each measured on Y rows the front end derotated with the STF increment alone,
+// and the per-symbol table the front ends then derotate with (rx_front_args::sto_sym)
+struct rx_sto_args {
+    uint32_t N_RX, Nf_pad, n_sym_total, n_drs, n_dops, N_occ, is_pdc;
+    uint32_t sym_first, sym_last;  // the phase's symbols: the table entries it fills (the PCC phase from the STF, 0)
+    double gain;            // scales each residual before it is added to the running increment
+    const uint32_t* dl;     // the phase plan's DRS ops (rx_snr_args)
+    const uint32_t* dmeta;
+    const uint32_t* drs_k;
+    const float* drs_v;
+    const float2* Y;
+    rx_pkt_state* st;
+    const uint32_t* sel;    // launch packet -> slot / output row
+    double* tab;            // [slot][n_sym_total]
+};
+hipError_t launch_rx_sto_track(const rx_sto_args& a, uint32_t n, hipStream_t st);
 
 struct rx_lut {             // one Wiener LUT: [T][4][Nf] pilot | weight << 16, weights [n_vec][n]
     const uint32_t* pw;

@@ -72,6 +72,12 @@ __device__ __forceinline__ void extract_bins(const rx_front_args& A, const float
     *dst = cscale(v, A.amp_scale);
 }
 
+// STO derotation of subcarrier index k (zero at DC, estimator_sto.cpp:163-171): one expression for the
+// per-packet table rot[] and the per-symbol values of residual STO tracking, so equal increments give equal bits
+__device__ __forceinline__ float2 sto_rot(double inc, uint32_t N, uint32_t k) {
+    return phasor(-inc * static_cast<double>(N / 2) + inc * static_cast<double>(k));
+}
+
 // ===================================================================== STF
 // float2 slots of rx_stf_kernel's input staging, which also holds the FFT's two Nd buffers
 __host__ __device__ inline uint32_t rx_stf_in(uint32_t n_stf, uint32_t Nd, uint32_t M, uint32_t L, uint32_t hl) {
@@ -355,7 +361,8 @@ __global__ void __launch_bounds__(256) rx_stf_kernel(rx_front_args A) {
         inc += static_cast<double>(atan2f(static_cast<float>(bi), static_cast<float>(br)) / 4.0f);
     }
     inc /= static_cast<double>(A.N_RX);
-    S.sto_inc = inc;
+    S.sto_inc = S.sto_run = inc;  // residual STO tracking starts from the STF estimate (rx_sto_track_kernel)
+    S.sto_ops = S.pad0 = 0;
     S.sto_frac = static_cast<float>(atan2(sin(inc), cos(inc)) / 2.0 / 3.14159265358979323846 * Nd);
     // STF SNR on the derotated symbol (estimator_snr.cpp:48-66,104-146)
     double sn = 0.0, nn = 0.0;
@@ -392,7 +399,9 @@ __host__ __device__ inline uint32_t rx_in_cap(uint32_t Nd, uint32_t CP, uint32_t
     return ((pass * (Nd + CP)) * M + L - 1) / L + W + 2 * M + 2 * L;
 }
 
-template <int LR, int MR, int HLR>
+// TRK: residual STO tracking (A.sto_sym set), every symbol derotated with its own table entry instead of
+// rot[]; an instantiation of its own, so the default one keeps its registers (64 VGPRs: 8 waves per SIMD)
+template <int LR, int MR, int HLR, bool TRK = false>
 __global__ void __launch_bounds__(RX_THREADS) rx_fft_kernel(rx_front_args A) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     const uint32_t Nd = A.plan.N, N = A.N_occ, Nf = N + 1;
@@ -419,7 +428,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_fft_kernel(rx_front_args A) {
     const rx_pkt_state S = A.st[pkt];
     const uint32_t n_stf = A.STF_CP + Nd;
     for (uint32_t k = threadIdx.x; k < Nf; k += RX_THREADS)
-        rot[k] = phasor(-S.sto_inc * static_cast<double>(N / 2) + S.sto_inc * static_cast<double>(k));
+        rot[k] = sto_rot(S.sto_inc, N, k);
     const float2* x = A.iq + (size_t(in.win) * A.N_RX + a) * A.S_in;
     const double phi_stf = static_cast<double>(n_stf) * in.inc0;  // mixer phase at the first data sample
     const float2 step1 = phasor(S.inc1);
@@ -470,7 +479,12 @@ __global__ void __launch_bounds__(RX_THREADS) rx_fft_kernel(rx_front_args A) {
             const uint32_t s = i / Nf, k = i - s * Nf;
             float2 v;
             extract_bins(A, F + s * Nd, &v, k);
-            A.Y[((size_t(pkt) * A.N_RX + a) * A.n_sym_total + lp + s) * A.Nf_pad + k] = cmul(v, rot[k]);
+            float2 r = rot[k];
+            if constexpr (TRK) {  // the symbol's own increment, rot[]'s expression per bin
+                const double si = A.sto_sym[size_t(pkt) * A.n_sym_total + lp + s];
+                r = sto_rot(si, N, k);
+            }
+            A.Y[((size_t(pkt) * A.N_RX + a) * A.n_sym_total + lp + s) * A.Nf_pad + k] = cmul(v, r);
         }
         __syncthreads();
     }
@@ -585,7 +599,7 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
         rx_resample_ct<LR, MR, HLR>(A, in, S, sp, R, lane);
         // one instantiation of the (large, unrolled) FFT for both kinds of symbol: instruction cache
         const bool to_y = !A.no_y;
-        rx_fft_bins<RT>(A, S, R, lane, [&](uint32_t k, float2 v) {
+        rx_fft_bins<RT>(A, rx_sto_of(A, S, pkt, l), R, lane, [&](uint32_t k, float2 v) {
             if (to_y) Yrow[k] = v;
             if (drs) R[k] = v;
         }, w1, wl);
@@ -625,7 +639,7 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
         // table path: twiddles from LDS (rx_fft_bins reads them through A.tw)
         rx_front_args B = A;
         B.tw = twl;
-        rx_fft_bins(B, S, R, lane, [&](uint32_t k, float2 v) {
+        rx_fft_bins(B, rx_sto_of(A, S, pkt, l), R, lane, [&](uint32_t k, float2 v) {
             Yrow[k] = v;
             if (drs) R[k] = v;
         });
@@ -701,7 +715,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) rx
             row_rsrc(A.Y + ((size_t(pkt) * A.N_RX + a) * A.n_sym_total + l) * A.Nf_pad, to_y ? A.Nf_pad * 8u : 0u);
         const bool drs = so != 0xFFFFu;
         if constexpr (!experiment(XS_FE_SKIP_FIR)) rx_resample_ct<LR, MR, HLR>(A, in, S, sp, R, lane);
-        rx_fft_bins<true>(A, S, R, lane, [&](uint32_t k, float2 v) {
+        rx_fft_bins<true>(A, rx_sto_of(A, S, pkt, l), R, lane, [&](uint32_t k, float2 v) {
             // Y is written once and read by the next launch: nontemporal stores when that launch
             // comes after the whole batch, plain ones when it follows within a cache-sized group
             typedef uint32_t u2v __attribute__((ext_vector_type(2)));
@@ -782,11 +796,11 @@ hipError_t launch_rx_fft(const rx_front_args& a_in, uint32_t n, hipStream_t st) 
             hipLaunchKernelGGL((rx_fft_wave_kernel<9, 10, 24, false>), g, b, lds, st, a);
         }
     } else if (a.L == 9 && a.M == 10 && a.hl == 24)  // os_min 1 (225 taps)
-        fast(rx_fft_kernel<9, 10, 24>);
+        a.sto_sym ? fast(rx_fft_kernel<9, 10, 24, true>) : fast(rx_fft_kernel<9, 10, 24>);
     else if (a.L == 9 && a.M == 10 && a.hl == 4)  // os_min 2
-        fast(rx_fft_kernel<9, 10, 4>);
+        a.sto_sym ? fast(rx_fft_kernel<9, 10, 4, true>) : fast(rx_fft_kernel<9, 10, 4>);
     else
-        fast(rx_fft_kernel<0, 0, 0>);
+        a.sto_sym ? fast(rx_fft_kernel<0, 0, 0, true>) : fast(rx_fft_kernel<0, 0, 0>);
     return hipGetLastError();
 }
 

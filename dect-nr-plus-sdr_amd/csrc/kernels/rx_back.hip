@@ -4,6 +4,9 @@
 //                   accumulation (estimator_snr.cpp:104-146) and the SNR-driven Wiener LUT profile
 //                   pick after each DRS symbol (rx_synced.cpp:863-891). One wavefront per DRS
 //                   symbol; the accumulation itself is a short serial prefix.
+//  rx_sto_track_kernel  one WG per packet, only with residual STO tracking on: the STO increment after
+//                   every DRS symbol of the phase and the per-symbol table the front ends derotate with
+//                   (estimator_sto.cpp:64-97, 148-171).
 //  rx_cells_kernel  one WG per (packet, epoch): an epoch is a run of cell work over which the
 //                   interlaced pilot buffer (channel_antenna.hpp:38-63) does not change. The WG
 //                   rebuilds that buffer in LDS from the zero-forced DRS cells of Y, then every
@@ -155,6 +158,85 @@ hipError_t launch_rx_snr(const rx_snr_args& a, uint32_t n, hipStream_t st) {
         case 8: hipLaunchKernelGGL(rx_snr_kernel<8>, dim3(n), dim3(SNR_THREADS), 0, st, a); break;
         default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// ===================================================================== residual STO tracking
+// The reference's second STO stage (RX_SYNCED_PARAM_STO_RESIDUAL_BASED_ON_DRS, compiled out in its default
+// build): after every DRS symbol the slope of the zero-forced pilots over frequency is added to the
+// running increment (estimator_sto.cpp:64-97), and every later symbol is derotated with the new value
+// (rx_synced.cpp:767-770). Here the DRS rows of the phase are in Y, derotated with the STF increment alone;
+// rotating them by exp(j delta (k - N_b_OCC/2)), delta = running - STF increment, gives the pilots the
+// reference measures. One wavefront per (RX antenna, transmit stream) of an op: the pilot products in
+// float (as rx_drs_partials'), their sums, the angles, the recurrence and the table in double. The
+// DC-straddling pair is 5 subcarriers apart and divided by 4 like the others (estimator_sto.cpp:160).
+constexpr uint32_t STO_THREADS = 256;
+constexpr uint32_t STO_TS_MAX = 8;  // RX_SYNCED_PARAM_STO_RESIDUAL_BASED_ON_DRS_N_TS_MAX
+
+__global__ void __launch_bounds__(STO_THREADS) rx_sto_track_kernel(rx_sto_args A) {
+    __shared__ double ang[8 * STO_TS_MAX];  // per (rx, stream) of the op
+    const uint32_t pkt = rx_slot_of(A.sel, blockIdx.x), nd = A.n_drs;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, nw = STO_THREADS / 64;
+    const size_t ast = size_t(A.n_sym_total) * A.Nf_pad;
+    const float2* Yp = A.Y + size_t(pkt) * A.N_RX * ast;
+    double* tab = A.tab + size_t(pkt) * A.n_sym_total;
+    rx_pkt_state* st = A.st + pkt;
+    const double inc0 = st->sto_inc, half = static_cast<double>(A.N_occ / 2);
+    // the PDC phase continues where the PCC phase stopped (and leaves that state as it is: a second PDC
+    // call on the same PCC batch starts from it again); every thread carries the same recurrence
+    double run = A.is_pdc ? st->sto_run : inc0;
+    uint32_t d = A.is_pdc ? st->sto_ops : 0u, lf = A.sym_first;
+    for (; d < A.n_dops; ++d) {
+        const uint32_t l = A.dl[d], meta = A.dmeta[d];
+        if (l > A.sym_last) break;
+        // a DRS symbol itself is derotated with the value from before its own update (run_cp_fft_scale
+        // comes before run_drs_chestim_zf)
+        for (uint32_t s = lf + threadIdx.x; s <= l; s += STO_THREADS) tab[s] = run;
+        lf = max(lf, l + 1);
+        const uint32_t tf = meta & 0xFFu, tl = min((meta >> 8) & 0xFFu, STO_TS_MAX - 1), par = (meta >> 16) & 0xFFu;
+        const uint32_t nts = tl >= tf ? tl - tf + 1 : 0u, cnt = A.N_RX * nts;
+        const double delta = run - inc0;
+        const float2* rows = Yp + size_t(l) * A.Nf_pad;
+        for (uint32_t p = wave; p < cnt; p += nw) {
+            const uint32_t a = p / nts, t = tf + p % nts;
+            const uint32_t* __restrict__ kb = A.drs_k + (par * 4 + (t & 3u)) * nd;
+            const float* __restrict__ vv = A.drs_v + t * nd;
+            double br = 0.0, bi = 0.0;
+            for (uint32_t i = lane; i + 1 < nd; i += 64) {
+                const uint32_t k0 = kb[i], k1 = kb[i + 1];
+                float2 h0 = cscale(rows[a * ast + k0], vv[i]), h1 = cscale(rows[a * ast + k1], vv[i + 1]);
+                if (delta != 0.0) {
+                    h0 = cmul(h0, phasor(delta * (static_cast<double>(k0) - half)));
+                    h1 = cmul(h1, phasor(delta * (static_cast<double>(k1) - half)));
+                }
+                const float2 c = cmulc(h0, h1);
+                br += c.x;
+                bi += c.y;
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                br += __shfl_xor(br, o);
+                bi += __shfl_xor(bi, o);
+            }
+            if (lane == 0) ang[p] = atan2(bi, br) / static_cast<double>(prm::N_STF_CELLS_SPACING);
+        }
+        __syncthreads();
+        if (cnt) {  // cnt = 0: the stream limit leaves nothing to measure, no update (estimator_sto.cpp:86-88)
+            double s = 0.0;
+            for (uint32_t p = 0; p < cnt; ++p) s += ang[p];
+            run += A.gain * (s / static_cast<double>(cnt));
+        }
+        __syncthreads();
+    }
+    for (uint32_t s = lf + threadIdx.x; s <= A.sym_last; s += STO_THREADS) tab[s] = run;
+    if (!A.is_pdc && threadIdx.x == 0) {
+        st->sto_run = run;
+        st->sto_ops = d;
+    }
+}
+
+hipError_t launch_rx_sto_track(const rx_sto_args& a, uint32_t n, hipStream_t st) {
+    if (a.N_RX > 8 || a.n_dops > MAX_DOPS || a.sym_last >= a.n_sym_total || a.sym_first > a.sym_last) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rx_sto_track_kernel, dim3(n), dim3(STO_THREADS), 0, st, a);
     return hipGetLastError();
 }
 

@@ -94,8 +94,9 @@ __device__ __forceinline__ void rx_resample_ct(const rx_front_args& A, const rx_
 // put is called (all exchange reads have completed).
 // RT: wave_fft1024_rt with the lane's two twiddles w1 = W^(4 (lane & 15)), wl = W^lane loaded by the
 // caller (e.g. before its input staging) instead of 27 twiddle loads inside the passes
+// sto_inc: the symbol's STO increment per subcarrier (rx_sto_of: the packet's, or the tracking table's)
 template <bool RT = false, class Put>
-__device__ __forceinline__ void rx_fft_bins(const rx_front_args& A, const rx_pkt_state& S, float2* R, uint32_t lane,
+__device__ __forceinline__ void rx_fft_bins(const rx_front_args& A, const double sto_inc, float2* R, uint32_t lane,
                                             Put&& put, float2 w1 = float2{}, float2 wl = float2{}) {
     float2 v[16];
 #pragma unroll
@@ -109,11 +110,11 @@ __device__ __forceinline__ void rx_fft_bins(const rx_front_args& A, const rx_pkt
         wave_fft1024<-1>(v, R, A.tw, lane);  // twiddles through the L1 (8 KB, every wave)
     __builtin_amdgcn_wave_barrier();
     const uint32_t N = A.N_occ;
-    const float2 s64 = phasor(64.0 * S.sto_inc);
+    const float2 s64 = phasor(64.0 * sto_inc);
     // the amplitude folded into the two derotation phasors: one complex product per bin (A/B per
     // 16384-slot PDC launch: 19.05 / 18.97 -> 18.82 / 18.55 ms)
-    float2 pa = cscale(phasor(S.sto_inc * static_cast<double>(lane)), A.amp_scale);
-    float2 pb = cscale(phasor(S.sto_inc * (static_cast<double>(lane) - static_cast<double>(A.off_lower) -
+    float2 pa = cscale(phasor(sto_inc * static_cast<double>(lane)), A.amp_scale);
+    float2 pb = cscale(phasor(sto_inc * (static_cast<double>(lane) - static_cast<double>(A.off_lower) -
                                            static_cast<double>(N / 2))), A.amp_scale);
     if (N == 896 && A.off_lower == 576) {  // beta = 16 at N_b_DFT_os = 1024 (C3 / C4): the bin map is static
         // rows m <= 6 lower half (k = n + 448), row 7 only n = 448 (k = 896), row 8 empty, rows >= 9
@@ -145,6 +146,12 @@ __device__ __forceinline__ void rx_fft_bins(const rx_front_args& A, const rx_pkt
         pa = cmul(pa, s64);
         pb = cmul(pb, s64);
     }
+}
+
+// the increment symbol l of a slot is derotated with: the STF estimate, or with residual STO tracking
+// (A.sto_sym, a uniform test) the table entry rx_sto_track_kernel wrote for the symbol
+__device__ __forceinline__ double rx_sto_of(const rx_front_args& A, const rx_pkt_state& S, uint32_t slot, uint32_t l) {
+    return A.sto_sym ? A.sto_sym[size_t(slot) * A.n_sym_total + l] : S.sto_inc;
 }
 
 // DRS SNR terms of one (antenna, DRS symbol) while its bins sit in the wave's region R (R[k] = bin

@@ -214,7 +214,8 @@ EXPORTS = ["dnrp_ctx_create", "dnrp_ctx_destroy", "dnrp_add_network_id", "dnrp_g
            "dnrp_pcc_encode_batch", "dnrp_query_table", "dnrp_ctx_set_rx_mode", "dnrp_ctx_set_tx_windowing",
            "dnrp_tx_window", "dnrp_ctx_set_sync_beta_search", "dnrp_ctx_get_sync_beta_search",
            "dnrp_ctx_set_sync_fine_all_antennas", "dnrp_ctx_get_sync_fine_all_antennas", "dnrp_rx_sync_fine_peaks",
-           "dnrp_tx_last_form", "dnrp_tx_form_for"]
+           "dnrp_tx_last_form", "dnrp_tx_form_for", "dnrp_ctx_set_rx_sto_tracking", "dnrp_ctx_get_rx_sto_tracking",
+           "dnrp_rx_sto_track"]
 
 _lib = None
 
@@ -251,6 +252,9 @@ def lib():
         L.dnrp_ctx_set_sync_fine_all_antennas.argtypes = [P, C.c_uint32]
         L.dnrp_ctx_get_sync_fine_all_antennas.argtypes = [P, C.POINTER(C.c_uint32)]
         L.dnrp_rx_sync_fine_peaks.argtypes = [P, C.c_uint32, P, P, P]
+        L.dnrp_ctx_set_rx_sto_tracking.argtypes = [P, C.c_uint32, C.c_float]
+        L.dnrp_ctx_get_rx_sto_tracking.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+        L.dnrp_rx_sto_track.argtypes = [P, C.c_uint32, P, C.c_uint32, C.POINTER(C.c_uint32), P]
         L.dnrp_ring_gather.argtypes = [P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, P, C.c_uint32, P, P]
         L.dnrp_channel_batch.argtypes = [P, C.POINTER(ChannelCfg), C.c_uint32, C.c_uint32, P, C.c_uint32, C.c_uint32, P, P,
                                          P, C.c_uint32, P]
@@ -519,6 +523,33 @@ class Phy:
                                            C.c_void_p(index.ctypes.data), _stream_ptr(stream)), "dnrp_rx_sync_fine_peaks")
         self.sync(stream)
         return metric, index
+
+    def set_rx_sto_tracking(self, on, gain=1.0):
+        """dnrp_ctx_set_rx_sto_tracking: every later rx_pcc_batch (and its rx_pdc_batch) adds, after each DRS
+        symbol, gain times the slope of its zero-forced pilots over frequency to the STO increment the later
+        symbols are derotated with (the reference's build option RX_SYNCED_PARAM_STO_RESIDUAL_BASED_ON_DRS);
+        off (the default) derotates every symbol with the STF estimate."""
+        _chk(lib().dnrp_ctx_set_rx_sto_tracking(self._ctx, int(on), float(gain)), "dnrp_ctx_set_rx_sto_tracking")
+
+    def rx_sto_tracking(self):
+        """dnrp_ctx_get_rx_sto_tracking: (on, gain)."""
+        on, gain = C.c_uint32(), C.c_float()
+        _chk(lib().dnrp_ctx_get_rx_sto_tracking(self._ctx, C.byref(on), C.byref(gain)), "dnrp_ctx_get_rx_sto_tracking")
+        return bool(on.value), gain.value
+
+    def rx_sto_track(self, n_slots, stream=None):
+        """dnrp_rx_sto_track: float64 [n_slots, n_sym], the STO increment each OFDM symbol of the first n_slots
+        PCC-batch slots was derotated with by the latest rx_pcc_batch / rx_pdc_batch, which ran with
+        set_rx_sto_tracking(1): symbol 0 the STF estimate, NaN where a symbol was not processed. Synchronises
+        the stream before it returns."""
+        n_sym = C.c_uint32()
+        _chk(lib().dnrp_rx_sto_track(self._ctx, int(n_slots), None, 0, C.byref(n_sym), _stream_ptr(stream)),
+             "dnrp_rx_sto_track")
+        inc = np.full((int(n_slots), n_sym.value), np.nan, np.float64)
+        _chk(lib().dnrp_rx_sto_track(self._ctx, int(n_slots), C.c_void_p(inc.ctypes.data), n_sym.value, C.byref(n_sym),
+                                     _stream_ptr(stream)), "dnrp_rx_sto_track")
+        self.sync(stream)
+        return inc
 
     def add_network_id(self, nid):
         _chk(lib().dnrp_add_network_id(self._ctx, nid), "dnrp_add_network_id")

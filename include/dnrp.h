@@ -384,6 +384,38 @@ int dnrp_sync(dnrp_ctx* ctx, void* stream);
 int dnrp_ctx_set_rx_mode(dnrp_ctx* ctx, uint32_t flags);
 
 /*
+ * Residual STO tracking from the DRS symbols <- the build option RX_SYNCED_PARAM_STO_RESIDUAL_BASED_ON_DRS
+ * (lib/include/dectnrp/phy/rx/rx_synced/rx_synced_param.hpp:156; rx_synced.cpp:767-770, 839-841,
+ * estimator_sto.cpp:64-97, 148-171), which the reference's default build leaves out.
+ *   on  0 (default): exactly the receiver without the option: every symbol of a packet is derotated with
+ *       the STO increment estimated from the STF, the same launches, byte-identical LLRs and reports.
+ *       1: after every DRS symbol the slope over frequency of its zero-forced pilots -- per RX antenna and
+ *       transmit stream TS_first..min(TS_last, 7) the angle of sum_i h[i] conj(h[i + 1]) over the stream's
+ *       DRS cells divided by 4, averaged over (antenna, stream) -- times `gain` is added to the running
+ *       increment, and every later symbol is derotated with the new value (a DRS symbol itself with the
+ *       value from before its own update). This follows a sampling-clock offset over a long packet. The
+ *       PDC phase continues from the PCC phase's state. The fused receiver (DNRP_RX_FUSED) and the grouped
+ *       Y path (DNRP_RX_GROUP) are not taken while it is on.
+ *   gain  scales each residual before it is added: 1 is the reference, 0 runs the whole mechanism with
+ *       every symbol's increment equal to the STF estimate (LLRs byte-identical to off).
+ * Read once per dnrp_rx_pcc_batch; that call's dnrp_rx_pdc_batch takes the same values. With it on, a
+ * dnrp_rx_pdc_batch request for spatial multiplexing (DNRP_RX_MODE_SM_MMSE, N_SS > 1) returns
+ * DNRP_EUNSUPPORTED before anything is launched. DNRP_EINVAL for a NULL context, on > 1, a non-finite gain or
+ * a gain outside [0, 1]; a refused call changes nothing. The getter's outputs may be NULL.
+ *
+ * dnrp_rx_sto_track: stream-ordered copy of the increment every OFDM symbol was derotated with by the latest
+ * dnrp_rx_pcc_batch / dnrp_rx_pdc_batch: inc is a host array [n_slots][*n_sym], slot = index in the PCC batch,
+ * *n_sym = symbols the PCC call's windows hold + 1. Symbol 0 holds the STF estimate, symbols that were not
+ * processed (behind the PCC phase of a packet no PDC request continued, behind a packet's end) hold NaN.
+ * inc NULL: only *n_sym is written (size query). Valid once `stream` has been synchronised.
+ * DNRP_EINVAL while the latest PCC call ran with tracking off or there was none, for n_slots = 0 or beyond
+ * that call's n, or n_sym_cap < *n_sym.
+ */
+int dnrp_ctx_set_rx_sto_tracking(dnrp_ctx* ctx, uint32_t on, float gain);
+int dnrp_ctx_get_rx_sto_tracking(const dnrp_ctx* ctx, uint32_t* on, float* gain);
+int dnrp_rx_sto_track(dnrp_ctx* ctx, uint32_t n_slots, double* inc, uint32_t n_sym_cap, uint32_t* n_sym, void* stream);
+
+/*
  * Ring-buffer window gather <- rx_pacer_t's wrap copy (rx_pacer.cpp:106-143) over the per-antenna
  * ring of radio::buffer_rx_t (radio/buffer_rx.hpp:46-141; sample of global time t at index
  * t % ring_len). Copies window w = global samples [start[w], start[w] + S_win) of antennas
