@@ -179,6 +179,11 @@ struct rx2_tables {  // per (psdef): PDC phase
     // MIMO report (estimator_mimo_t): wideband DRS cells, single-stream codebooks
     uint32_t N_TS = 1, ncb_tx = 0, A_tx = 0, ncb_rx = 0, A_rx = 0;
     dbuf mimo_cells, mimo_signs, Wtx, stx, Wrx, srx;
+    // rx_mimo_detail_kernel (dnrp_ctx_set_rx_mimo_report): the spatial-multiplexing codebooks (R, N_TS) of the
+    // rank slots R = 1, 2, 4 back to back in Wsm [entry][antenna][layer] / ssm (scaling factors): entries per
+    // slot (0: rank not available at this N_TS), the slot's first float2 in Wsm and first entry in ssm
+    uint32_t sm_ncb[3] = {}, sm_woff[3] = {}, sm_cboff[3] = {};
+    dbuf Wsm, ssm;
     // fused PDC receiver (kernels/rx_fused.hip): its symbol table, the phase's DRS symbols the front
     // end runs first (after the PCC phase's), whether those carry PDC cells (their bins then go to Y),
     // and the MIMO report's wideband cells in the zero-forced pilots (op << 16 | DRS cell)
@@ -336,6 +341,12 @@ struct dnrp_ctx {
     bool rx_sto_on = false;
     float rx_sto_gain = 1.0f;
     dbuf sto_sym;
+    // MIMO report options (dnrp_ctx_set_rx_mimo_report): the setting, read once per dnrp_rx_pdc_batch.
+    // mimo_rows: one dnrp_mimo_detail per request of the latest PDC call that ran rx_mimo_detail_kernel, sized
+    // like mimo_out; mimo_rows_m: that call's m where it ran with detail = 1, else 0 (dnrp_rx_mimo_detail)
+    uint32_t mimo_metric = 0, mimo_all_w = 0, mimo_detail = 0;
+    uint32_t mimo_rows_m = 0;
+    dbuf mimo_rows;
     pinned st_tx, st_rxin, st_seq, st_rep;
     // retained RX phase-1 state: per PCC-batch slot its (u, b, N_eff_TX) tables and symbol
     // capacity; Y is laid out with the batch-wide maxima rx_nsym_cap / rx_Nf_pad

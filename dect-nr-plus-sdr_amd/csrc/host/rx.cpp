@@ -374,7 +374,7 @@ int pdc_plain_y(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_
 // MIMO report at the packet end (rx_synced.cpp:417-436; the reference runs it after a successful CRC,
 // which is the caller's decision here). fa.zd set: the fused receiver ran, the DRS bins of this phase
 // are not in Y and the pilots hold the same values
-int pdc_mimo(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const dev::rx_front_args& fa, hipStream_t st) {
+dev::rx_mimo_args mimo_args(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const dev::rx_front_args& fa) {
     dev::rx_mimo_args ma{};
     ma.N_RX = ctx->cfg.N_TX_max;
     ma.N_TS = t2->N_TS;
@@ -399,11 +399,52 @@ int pdc_mimo(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const dev::
         ma.zd_dops = fa.zd_dops;
         ma.zd_row = fa.zd_row;
     }
-    return dev::launch_rx_mimo(ma, p.n, st) == hipSuccess ? DNRP_OK : DNRP_EDEVICE;
+    return ma;
 }
 
-// one launch group of the PDC call: its receiver, then the MIMO report where the caller asked for reports
-int pdc_group(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const float* iq_in, bool mimo, hipStream_t st) {
+int pdc_mimo(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const dev::rx_front_args& fa, hipStream_t st) {
+    return dev::launch_rx_mimo(mimo_args(ctx, p, t2, fa), p.n, st) == hipSuccess ? DNRP_OK : DNRP_EDEVICE;
+}
+
+// the same report through rx_mimo_detail_kernel under a non-default dnrp_ctx_set_rx_mimo_report (o: what the
+// PDC call read of it): the chosen metric and search start, every score, the rank / precoder report. The
+// noise variance is the nv_d entry of the phase's last DRS op, which rx_snr_kernel writes on every PDC path
+// (launch_back and launch_snr_chain run it over all of the plan's ops for all of the group's packets; the
+// grouped Y path's auxiliary stream has joined st by now)
+struct mimo_opts {
+    uint32_t metric = 0, all_w = 0, detail = 0;
+    bool on() const { return metric || all_w || detail; }
+};
+
+static_assert(sizeof(dev::rx_mimo_detail_row) == sizeof(dnrp_mimo_detail), "dnrp_mimo_detail layout");
+static_assert(dev::RX_MIMO_MAX_CB == DNRP_MIMO_MAX_CB, "DNRP_MIMO_MAX_CB");
+
+int pdc_mimo_detail(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const dev::rx_front_args& fa,
+                    const mimo_opts& o, hipStream_t st) {
+    dev::rx_mimo_detail_args da{};
+    da.M = mimo_args(ctx, p, t2, fa);
+    if (o.all_w) da.M.A_tx = da.M.A_rx = 0;
+    da.metric = o.metric;
+    da.n_dops = p.plan->n_dops;
+    da.nv_d = ctx->nv_d.as<float>();
+    for (int s = 0; s < 3; ++s) {
+        da.sm_ncb[s] = t2->sm_ncb[s];
+        da.sm_woff[s] = t2->sm_woff[s];
+        da.sm_cboff[s] = t2->sm_cboff[s];
+    }
+    da.Wsm = t2->Wsm.as<float2>();
+    da.ssm = t2->ssm.as<float>();
+    da.rows = ctx->mimo_rows.as<dev::rx_mimo_detail_row>();
+    ctx->tic("rx_mimo_detail", st);
+    if (dev::launch_rx_mimo_detail(da, p.n, st) != hipSuccess) return DNRP_EDEVICE;
+    ctx->toc("rx_mimo_detail", st);
+    return DNRP_OK;
+}
+
+// one launch group of the PDC call: its receiver, then the MIMO report where the caller asked for reports (or,
+// with the detailed report on, for its rows)
+int pdc_group(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const float* iq_in, bool mimo, const mimo_opts& mo,
+              hipStream_t st) {
     auto fa = front_args(ctx, p.t, iq_in, p.sel, snr_from_front(ctx, p.t) ? p.plan : nullptr);
     const auto ca = cells_args(ctx, p);
     const pdc_path path = choose_pdc_path(ctx->sw, p.t, t2, fa, ca, p.n, ctx->rx_sto_on);
@@ -423,7 +464,8 @@ int pdc_group(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const floa
         case pdc_path::grouped_y: err = pdc_grouped_y(ctx, p, t2, fa, st); break;
         case pdc_path::plain_y: err = pdc_plain_y(ctx, p, t2, fa, ca, st); break;
     }
-    return err == DNRP_OK && mimo ? pdc_mimo(ctx, p, t2, fa, st) : err;
+    if (err != DNRP_OK || !mimo) return err;
+    return mo.on() ? pdc_mimo_detail(ctx, p, t2, fa, mo, st) : pdc_mimo(ctx, p, t2, fa, st);
 }
 
 // the PDC reports of the call: the SNR chain's PDC estimate and the MIMO report of every request
@@ -652,7 +694,13 @@ int dnrp_rx_pdc_batch(dnrp_ctx* ctx, uint32_t m, const dnrp_pdc_req* req, const 
     HIPCHK(hipEventRecord(ctx->st_seq.ev, st));
     HIPCHK(hipMemcpyAsync(ctx->rx_sel2.p, sel, 2 * sizeof(uint32_t) * m, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(ctx->st_sel2.ev, st));
-    if (rep && !ctx->mimo_out.ensure(size_t(ctx->cfg.max_batch) * 3 * sizeof(uint32_t))) return DNRP_ENOMEM;
+    // the MIMO report options, read once per call: the default runs rx_mimo_kernel where the caller takes reports,
+    // as ever; any other setting runs rx_mimo_detail_kernel there, and with detail = 1 for its rows alone too
+    const mimo_opts mo{ctx->mimo_metric, ctx->mimo_all_w, ctx->mimo_detail};
+    const bool mimo = rep != nullptr || mo.detail != 0;
+    ctx->mimo_rows_m = 0;
+    if (mimo && !ctx->mimo_out.ensure(size_t(ctx->cfg.max_batch) * 3 * sizeof(uint32_t))) return DNRP_ENOMEM;
+    if (mimo && mo.on() && !ctx->mimo_rows.ensure(size_t(ctx->cfg.max_batch) * sizeof(dnrp_mimo_detail))) return DNRP_ENOMEM;
     uint32_t off = 0;
     size_t gi = 0;
     for (const auto& g : groups) {
@@ -663,10 +711,37 @@ int dnrp_rx_pdc_batch(dnrp_ctx* ctx, uint32_t m, const dnrp_pdc_req* req, const 
         off += ng;
         const rx_phase p{t, &t2->bplan, ng, gsel, true, t2->q.N_bps, t2->pdc_k.as<uint32_t>(), t2->pdc_sym.as<uint16_t>(),
                          pdc_llr, llr_stride, t2->sm};
-        err = pdc_group(ctx, p, t2, iq_in, rep != nullptr, st);
+        err = pdc_group(ctx, p, t2, iq_in, mimo, mo, st);
         if (err != DNRP_OK) return err;
     }
+    if (mo.detail) ctx->mimo_rows_m = m;
     return rep ? pdc_reports(ctx, m, req, rep, st) : DNRP_OK;
+}
+
+int dnrp_ctx_set_rx_mimo_report(dnrp_ctx* ctx, uint32_t metric, uint32_t all_w, uint32_t detail) {
+    if (!ctx || metric > DNRP_MIMO_METRIC_MIN_SPREAD_RX_POWER || all_w > 1 || detail > 1) return DNRP_EINVAL;
+    ctx->mimo_metric = metric;
+    ctx->mimo_all_w = all_w;
+    ctx->mimo_detail = detail;
+    return DNRP_OK;
+}
+
+int dnrp_ctx_get_rx_mimo_report(const dnrp_ctx* ctx, uint32_t* metric, uint32_t* all_w, uint32_t* detail) {
+    if (!ctx) return DNRP_EINVAL;
+    if (metric) *metric = ctx->mimo_metric;
+    if (all_w) *all_w = ctx->mimo_all_w;
+    if (detail) *detail = ctx->mimo_detail;
+    return DNRP_OK;
+}
+
+int dnrp_rx_mimo_detail(dnrp_ctx* ctx, uint32_t m, dnrp_mimo_detail* out, void* stream) {
+    if (!ctx || !out || m == 0) return DNRP_EINVAL;
+    if (!ctx->mimo_rows_m) return DNRP_ESTATE;
+    if (m > ctx->mimo_rows_m) return DNRP_EINVAL;
+    (void)hipSetDevice(ctx->cfg.device);
+    HIPCHK(hipMemcpyAsync(out, ctx->mimo_rows.p, size_t(m) * sizeof(dnrp_mimo_detail), hipMemcpyDeviceToHost,
+                          static_cast<hipStream_t>(stream)));
+    return DNRP_OK;
 }
 
 int dnrp_ctx_set_rx_sto_tracking(dnrp_ctx* ctx, uint32_t on, float gain) {

@@ -71,6 +71,33 @@ bool mimo_codebook(uint32_t N, dbuf& W, dbuf& sc, uint32_t& ncb, uint32_t& A0) {
     return W.upload(w) && sc.upload(s);
 }
 
+// rx_mimo_detail_kernel: the codebooks (R, N_TS) of the ranks R = 1, 2, 4 that N_TS transmit streams and N_RX
+// receive antennas carry, back to back. N_TS = 8 has none (W_t::get_W(1, 8) is the SISO entry, not taken)
+bool mimo_sm_codebooks(uint32_t N_TS, uint32_t N_RX, rx2_tables* t) {
+    std::vector<float2> w;
+    std::vector<float> s;
+    for (uint32_t slot = 0; slot < 3; ++slot) {
+        const uint32_t R = 1u << slot;
+        t->sm_woff[slot] = static_cast<uint32_t>(w.size());
+        t->sm_cboff[slot] = static_cast<uint32_t>(s.size());
+        t->sm_ncb[slot] = 0;
+        if (R > std::min(N_TS, N_RX) || (N_TS != 1 && N_TS != 2 && N_TS != 4)) continue;
+        const uint32_t ncb = geo::W_codebooks(R, N_TS);
+        if (ncb > dev::RX_MIMO_MAX_CB) return false;
+        t->sm_ncb[slot] = ncb;
+        for (uint32_t cb = 0; cb < ncb; ++cb) {
+            float f = 1.f;
+            for (const auto& v : geo::W_matrix(R, N_TS, cb, &f)) w.push_back(make_float2(v.real(), v.imag()));
+            s.push_back(f);
+        }
+    }
+    if (w.empty()) {  // non-empty uploads; the counts stay 0
+        w.push_back(make_float2(0.f, 0.f));
+        s.push_back(0.f);
+    }
+    return t->Wsm.upload(w) && t->ssm.upload(s);
+}
+
 }  // namespace
 
 namespace dnrp::host {
@@ -375,7 +402,9 @@ rx2_tables* get_rx2(dnrp_ctx* ctx, const dnrp_psdef& d, int* err) {
         if (v->empty()) v->push_back(0);  // non-empty uploads; the counts stay 0
     bool up = t->mimo_cells.upload(mc.cells) && t->mimo_signs.upload(mc.signs) && t->mimo_zcells.upload(mc.zcells) &&
               mimo_codebook(t->N_TS, t->Wtx, t->stx, t->ncb_tx, t->A_tx) &&
-              mimo_codebook(ctx->cfg.N_TX_max, t->Wrx, t->srx, t->ncb_rx, t->A_rx);
+              mimo_codebook(ctx->cfg.N_TX_max, t->Wrx, t->srx, t->ncb_rx, t->A_rx) &&
+              t->ncb_tx <= dev::RX_MIMO_MAX_CB && t->ncb_rx <= dev::RX_MIMO_MAX_CB &&
+              mimo_sm_codebooks(t->N_TS, ctx->cfg.N_TX_max, t.get());
     if (t->fused_ok) up = up && t->fsym.upload(fu.fsym) && t->drs_syms.upload(fu.drs_syms);
     if (t->ep_ok) up = up && t->ep_off.upload(ep.off) && t->ep_sym.upload(ep.sym) && t->ep_drs.upload(ep.drs);
     // the epoch receiver's plan with twin segments (same epochs and cells, so its symbol lists hold);

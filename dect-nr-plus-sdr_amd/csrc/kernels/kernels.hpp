@@ -378,6 +378,36 @@ struct rx_mimo_args {  // estimator_mimo_t::process_drs at the packet end, one w
 };
 hipError_t launch_rx_mimo(const rx_mimo_args& a, uint32_t n, hipStream_t st);
 
+// MIMO report with a chosen metric / search start, every candidate's score and the rank / precoder report for
+// spatial multiplexing (dnrp_ctx_set_rx_mimo_report): rx_mimo_detail_kernel in place of rx_mimo_kernel
+constexpr uint32_t RX_MIMO_MAX_CB = 28;  // DNRP_MIMO_MAX_CB: the largest codebook, (N_SS 1, N_TX 4)
+struct rx_mimo_detail_row {              // dnrp_mimo_detail, field for field (rx.cpp asserts the size)
+    uint32_t N_RX, N_TS;
+    float H[8][8][4][2];  // floats: the rows are 4-byte aligned
+    float nv, nv_used;
+    uint32_t idx_tx, idx_rx;
+    float score_tx[RX_MIMO_MAX_CB], score_rx[RX_MIMO_MAX_CB];
+    uint32_t RI, PMI;
+    uint32_t pmi[3];
+    float rate[3];
+    float rate_cb[3][RX_MIMO_MAX_CB];
+    float sinr_eff_dB;
+};
+struct rx_mimo_detail_args {
+    rx_mimo_args M;         // the stage's gather, the single-stream codebooks (A_tx / A_rx: the search starts) and out
+    uint32_t metric;        // DNRP_MIMO_METRIC_*
+    uint32_t n_dops;        // the phase plan's DRS ops: nv_d[slot][n_dops - 1] is the noise variance at the packet end
+    const float* nv_d;      // [slot][RX_MAX_DOPS] (rx_snr_kernel)
+    // spatial-multiplexing codebooks (R, N_TS) of the rank slots R = 1, 2, 4: sm_ncb[s] entries (0: the rank is
+    // not available), entry cb of slot s at Wsm + sm_woff[s] + cb N_TS R as [antenna][layer], its scaling
+    // factor at ssm[sm_cboff[s] + cb]
+    uint32_t sm_ncb[3], sm_woff[3], sm_cboff[3];
+    const float2* Wsm;
+    const float* ssm;
+    rx_mimo_detail_row* rows;  // [row]
+};
+hipError_t launch_rx_mimo_detail(const rx_mimo_detail_args& a, uint32_t n, hipStream_t st);
+
 
 // ---- ring-buffer window gather (ring.hip): buffer_rx_t ring -> linear windows (rx_pacer.cpp:106-143)
 constexpr int RING_PAIRS = 4;  // sample pairs per thread

@@ -157,6 +157,29 @@ class PdcReport(C.Structure):
                 ("tm_3_7_beamforming_idx", C.c_uint32), ("tm_3_7_beamforming_reciprocal_idx", C.c_uint32)]
 
 
+MIMO_METRIC_HIGHEST_MIN_RX_POWER, MIMO_METRIC_MAX_RX_POWER, MIMO_METRIC_MIN_SPREAD_RX_POWER = 0, 1, 2
+MIMO_MAX_CB = 28  # DNRP_MIMO_MAX_CB
+MIMO_NONE = 0xFFFFFFFF
+
+
+class MimoDetail(C.Structure):
+    """dnrp_mimo_detail: the MIMO report's stage, noise variance, candidate scores and the rank / precoder report
+    of one PDC request (dnrp_rx_mimo_detail)."""
+    _fields_ = [("N_RX", C.c_uint32), ("N_TS", C.c_uint32), ("H", C.c_float * 2 * 4 * 8 * 8), ("nv", C.c_float),
+                ("nv_used", C.c_float), ("idx_tx", C.c_uint32), ("idx_rx", C.c_uint32),
+                ("score_tx", C.c_float * MIMO_MAX_CB), ("score_rx", C.c_float * MIMO_MAX_CB), ("RI", C.c_uint32),
+                ("PMI", C.c_uint32), ("pmi", C.c_uint32 * 3), ("rate", C.c_float * 3),
+                ("rate_cb", C.c_float * MIMO_MAX_CB * 3), ("sinr_eff_dB", C.c_float)]
+
+
+MIMO_DETAIL_DTYPE = np.dtype([("N_RX", np.uint32), ("N_TS", np.uint32), ("H", np.complex64, (8, 8, 4)),
+                              ("nv", np.float32), ("nv_used", np.float32), ("idx_tx", np.uint32), ("idx_rx", np.uint32),
+                              ("score_tx", np.float32, (MIMO_MAX_CB,)), ("score_rx", np.float32, (MIMO_MAX_CB,)),
+                              ("RI", np.uint32), ("PMI", np.uint32), ("pmi", np.uint32, (3,)), ("rate", np.float32, (3,)),
+                              ("rate_cb", np.float32, (3, MIMO_MAX_CB)), ("sinr_eff_dB", np.float32)])
+assert MIMO_DETAIL_DTYPE.itemsize == C.sizeof(MimoDetail)
+
+
 class PdcReq(C.Structure):
     """dnrp_pdc_req: PLCF-announced psdef, slot in the preceding PCC batch, network ID, PLCF type."""
     _fields_ = [("psdef", PsDef), ("pcc_index", C.c_uint32), ("network_id", C.c_uint32), ("plcf_type", C.c_uint32)]
@@ -215,7 +238,7 @@ EXPORTS = ["dnrp_ctx_create", "dnrp_ctx_destroy", "dnrp_add_network_id", "dnrp_g
            "dnrp_tx_window", "dnrp_ctx_set_sync_beta_search", "dnrp_ctx_get_sync_beta_search",
            "dnrp_ctx_set_sync_fine_all_antennas", "dnrp_ctx_get_sync_fine_all_antennas", "dnrp_rx_sync_fine_peaks",
            "dnrp_tx_last_form", "dnrp_tx_form_for", "dnrp_ctx_set_rx_sto_tracking", "dnrp_ctx_get_rx_sto_tracking",
-           "dnrp_rx_sto_track"]
+           "dnrp_rx_sto_track", "dnrp_ctx_set_rx_mimo_report", "dnrp_ctx_get_rx_mimo_report", "dnrp_rx_mimo_detail"]
 
 _lib = None
 
@@ -255,6 +278,9 @@ def lib():
         L.dnrp_ctx_set_rx_sto_tracking.argtypes = [P, C.c_uint32, C.c_float]
         L.dnrp_ctx_get_rx_sto_tracking.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
         L.dnrp_rx_sto_track.argtypes = [P, C.c_uint32, P, C.c_uint32, C.POINTER(C.c_uint32), P]
+        L.dnrp_ctx_set_rx_mimo_report.argtypes = [P, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.dnrp_ctx_get_rx_mimo_report.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.dnrp_rx_mimo_detail.argtypes = [P, C.c_uint32, P, P]
         L.dnrp_ring_gather.argtypes = [P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, P, C.c_uint32, P, P]
         L.dnrp_channel_batch.argtypes = [P, C.POINTER(ChannelCfg), C.c_uint32, C.c_uint32, P, C.c_uint32, C.c_uint32, P, P,
                                          P, C.c_uint32, P]
@@ -550,6 +576,32 @@ class Phy:
                                      _stream_ptr(stream)), "dnrp_rx_sto_track")
         self.sync(stream)
         return inc
+
+    def set_rx_mimo_report(self, metric=0, all_w=0, detail=0):
+        """dnrp_ctx_set_rx_mimo_report: every later rx_pdc_batch searches the single-stream codebooks with
+        `metric` (MIMO_METRIC_*, the reference's build option RX_SYNCED_PARAM_MODE_3_7_METRIC) from entry 0
+        (all_w = 1, RX_SYNCED_PARAM_MIMO_USE_ALL_W_MATRICES_OR_ONLY_NON_ZERO) or from the first entry without a
+        zero; detail = 1 keeps one dnrp_mimo_detail row per request (rx_mimo_detail). (0, 0, 0), the default, is
+        the reference's default build."""
+        _chk(lib().dnrp_ctx_set_rx_mimo_report(self._ctx, int(metric), int(all_w), int(detail)),
+             "dnrp_ctx_set_rx_mimo_report")
+
+    def rx_mimo_report(self):
+        """dnrp_ctx_get_rx_mimo_report: (metric, all_w, detail)."""
+        me, aw, de = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _chk(lib().dnrp_ctx_get_rx_mimo_report(self._ctx, C.byref(me), C.byref(aw), C.byref(de)),
+             "dnrp_ctx_get_rx_mimo_report")
+        return me.value, aw.value, de.value
+
+    def rx_mimo_detail(self, m, stream=None):
+        """dnrp_rx_mimo_detail: numpy record array [m] of MIMO_DETAIL_DTYPE (fields are views: H complex64
+        [m, 8, 8, 4], score_tx / score_rx [m, 28], rate_cb [m, 3, 28], ...), row r = request r of the latest
+        rx_pdc_batch, which ran with set_rx_mimo_report(detail=1). Synchronises the stream before it returns."""
+        out = np.zeros(int(m), MIMO_DETAIL_DTYPE)
+        _chk(lib().dnrp_rx_mimo_detail(self._ctx, int(m), C.c_void_p(out.ctypes.data) if m else None, _stream_ptr(stream)),
+             "dnrp_rx_mimo_detail")
+        self.sync(stream)
+        return out
 
     def add_network_id(self, nid):
         _chk(lib().dnrp_add_network_id(self._ctx, nid), "dnrp_add_network_id")

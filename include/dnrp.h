@@ -52,7 +52,8 @@ extern "C" {
 #define DNRP_EDEVICE (-5)     /* HIP runtime error */
 #define DNRP_ENETID (-6)      /* network ID not registered with dnrp_add_network_id */
 #define DNRP_ESTATE (-7)      /* dnrp_rx_pdc_batch without a preceding dnrp_rx_pcc_batch; dnrp_rx_sync_fine_peaks
-                                 without a preceding dnrp_rx_sync_batch that ran with the setting on */
+                                 without a preceding dnrp_rx_sync_batch that ran with the setting on;
+                                 dnrp_rx_mimo_detail without a preceding dnrp_rx_pdc_batch that ran with detail = 1 */
 
 typedef struct dnrp_ctx dnrp_ctx;
 
@@ -414,6 +415,74 @@ int dnrp_ctx_set_rx_mode(dnrp_ctx* ctx, uint32_t flags);
 int dnrp_ctx_set_rx_sto_tracking(dnrp_ctx* ctx, uint32_t on, float gain);
 int dnrp_ctx_get_rx_sto_tracking(const dnrp_ctx* ctx, uint32_t* on, float* gain);
 int dnrp_rx_sto_track(dnrp_ctx* ctx, uint32_t n_slots, double* inc, uint32_t n_sym_cap, uint32_t* n_sym, void* stream);
+
+/*
+ * MIMO report options <- the build options RX_SYNCED_PARAM_MODE_3_7_METRIC and
+ * RX_SYNCED_PARAM_MIMO_USE_ALL_W_MATRICES_OR_ONLY_NON_ZERO (lib/include/dectnrp/phy/rx/rx_synced/
+ * rx_synced_param.hpp:273-286; estimator_mimo.cpp:162-271), a read-back of the report's inputs and scores, and
+ * the rank / precoder report for spatial multiplexing that mimo_report_t declares (RI, PMI, mimo_report.hpp:51-58)
+ * and the reference never fills.
+ *   metric  how the codebook search of tm_3_7_beamforming_idx / _reciprocal_idx combines, per candidate, the
+ *           receive side's |sum_tx sum_c H w| (float, the reference's order):
+ *           DNRP_MIMO_METRIC_HIGHEST_MIN_RX_POWER (default) their minimum, the largest wins (from -1e6);
+ *           DNRP_MIMO_METRIC_MAX_RX_POWER their sum in ascending antenna order, the largest wins (from -1e6);
+ *           DNRP_MIMO_METRIC_MIN_SPREAD_RX_POWER maximum - minimum, the smallest wins (from +1e6).
+ *           The combination is multiplied by the entry's scaling factor (the reference's comment says
+ *           "ignoring", its code multiplies). The first candidate in index order wins a tie.
+ *   all_w   0 (default): the search starts at the first entry without a zero element (2 for 2 antennas, 12 for
+ *           4); 1: at entry 0.
+ *   detail  1: every later dnrp_rx_pdc_batch keeps one dnrp_mimo_detail per request (also without `rep`).
+ * (0, 0, 0) is exactly the receiver without the options: rx_mimo_kernel, launched only where the caller passes
+ * `rep`, the same reports, no further launch, allocation or copy. Under any other setting
+ * rx_mimo_detail_kernel runs in its place for every request (timer "rx_mimo_detail"); with metric 0 and all_w 0
+ * it computes the same indices with the same arithmetic in the same order. Read once per dnrp_rx_pdc_batch; a
+ * retained PCC batch stays valid. Every PDC path (plain Y, grouped Y, epoch, fused) stays selectable: each runs
+ * rx_snr_kernel over all DRS ops of the phase, which leaves the noise variance the report reads. DNRP_EINVAL
+ * for a NULL context, metric > 2, all_w > 1 or detail > 1; a refused call changes nothing. The getter's
+ * outputs may be NULL.
+ *
+ * dnrp_mimo_detail (the extension is marked *):
+ *   H         the stage: the latest zero-forced DRS value of every (rx, transmit stream) at the 4 wideband
+ *             cells, as the search reads it
+ *   nv        the SNR chain's noise variance per RX cell after the packet's last DRS symbol (the value the MMSE
+ *             receiver of DNRP_RX_MODE_SM_MMSE regularises with); nv_used* = max(nv, 2^-14 P, FLT_MIN), P the
+ *             mean |H|^2 of the stage: a noise-free packet stays finite, the SINR is capped near 42 dB
+ *   idx_*     the report's two indices; score_*: metric times scaling of every scored index, NaN elsewhere. A
+ *             side with one antenna reports index 0 and no score, one with 8 antennas (no single-stream
+ *             codebook) 0xFFFFFFFF and no score
+ *   rate_cb*  [s][cb]: rank slot s = 0, 1, 2 stands for R = 1, 2, 4 layers, available iff R <= min(N_TS, N_RX)
+ *             and N_TS in {1, 2, 4} (codebook (R, N_TS) of W_t; none at N_TS = 8). Per wideband cell c, He =
+ *             H_c W_cb scaling_cb (N_RX x R), G = He^H He + nv_used I, r_c = sum_i -log2(nv_used [G^-1]_ii), the
+ *             sum over the layers of log2(1 + MMSE SINR); rate_cb = (r_0 + r_1 + r_2 + r_3) / 4 bits per cell
+ *   pmi*, rate*  the first maximum of rate_cb[s] and its rate; RI*: the R with the largest rate (a tie goes to
+ *             the lower rank), PMI* = pmi[slot of RI]; sinr_eff_dB* = 10 log10(2^(rate[RI] / RI) - 1), the
+ *             number a caller maps to an MCS (no CQI: the reference has no SINR-to-MCS table)
+ * dnrp_rx_mimo_detail: stream-ordered copy of rows 0..m-1 of the latest dnrp_rx_pdc_batch, in request order,
+ * valid once `stream` has been synchronised. DNRP_ESTATE if that call did not run with detail = 1 or there was
+ * none; DNRP_EINVAL for NULL pointers, m = 0 or m above that call's m.
+ */
+#define DNRP_MIMO_METRIC_HIGHEST_MIN_RX_POWER 0u
+#define DNRP_MIMO_METRIC_MAX_RX_POWER 1u
+#define DNRP_MIMO_METRIC_MIN_SPREAD_RX_POWER 2u
+#define DNRP_MIMO_MAX_CB 28u /* largest codebook of W_t: (N_SS 1, N_TX 4) */
+
+int dnrp_ctx_set_rx_mimo_report(dnrp_ctx* ctx, uint32_t metric, uint32_t all_w, uint32_t detail);
+int dnrp_ctx_get_rx_mimo_report(const dnrp_ctx* ctx, uint32_t* metric, uint32_t* all_w, uint32_t* detail);
+
+typedef struct {
+    uint32_t N_RX, N_TS;
+    float H[8][8][4][2];      /* [rx][ts][wideband cell] (re, im), zero beyond N_RX / N_TS */
+    float nv, nv_used;
+    uint32_t idx_tx, idx_rx;  /* = tm_3_7_beamforming_idx / _reciprocal_idx of the report */
+    float score_tx[DNRP_MIMO_MAX_CB], score_rx[DNRP_MIMO_MAX_CB];
+    uint32_t RI, PMI;         /* rank in {1, 2, 4} and its codebook index; 0 / 0xFFFFFFFF: none */
+    uint32_t pmi[3];          /* best codebook index per rank slot (R = 1, 2, 4), 0xFFFFFFFF: rank not available */
+    float rate[3];            /* its rate in bits per cell, NaN: not available */
+    float rate_cb[3][DNRP_MIMO_MAX_CB]; /* every candidate's rate, NaN where there is none */
+    float sinr_eff_dB;
+} dnrp_mimo_detail;
+
+int dnrp_rx_mimo_detail(dnrp_ctx* ctx, uint32_t m, dnrp_mimo_detail* out, void* stream);
 
 /*
  * Ring-buffer window gather <- rx_pacer_t's wrap copy (rx_pacer.cpp:106-143) over the per-antenna
