@@ -348,18 +348,22 @@ int oracle_tx(const uint32_t* cfg, const uint32_t* psdef, const uint32_t* desc_u
 // pick (rx_in_t). picks (nullable): up to picks_cap pairs (profile, SNR estimate in dB at the pick), one
 // per DRS operation in order, the profile being the one the estimate selects whatever the override;
 // *n_picks the number of DRS operations.
-int oracle_rx_picks(const uint32_t* cfg, const uint32_t* psdef, uint32_t N_RX, const float* iq, uint32_t S_in,
-                    int64_t fine_peak, double cfo_rad, uint32_t network_id, uint32_t plcf_type, int16_t* pcc_llr,
-                    int16_t* pdc_llr, float* pcc_llr_f, float* pdc_llr_f, float* meta, int use_float,
-                    const float* sync_rms, int sm_mmse, int pick_force, int pick_stale, float* picks,
-                    uint32_t picks_cap, uint32_t* n_picks) {
+//
+// oracle_rx_mutant: the same again, plus mutate, a test-only wrong receiver (rx_in_t::mutate), 0 for none.
+// oracle_rx_picks keeps its argument list: callers built against it stay valid.
+int oracle_rx_mutant(const uint32_t* cfg, const uint32_t* psdef, uint32_t N_RX, const float* iq, uint32_t S_in,
+                     int64_t fine_peak, double cfo_rad, uint32_t network_id, uint32_t plcf_type, int16_t* pcc_llr,
+                     int16_t* pdc_llr, float* pcc_llr_f, float* pdc_llr_f, float* meta, int use_float,
+                     const float* sync_rms, int sm_mmse, int pick_force, int pick_stale, float* picks,
+                     uint32_t picks_cap, uint32_t* n_picks, int mutate) {
     try {
         packet_sizes_t q;
         if (!get_packet_sizes(to_psdef(psdef), q)) return -1;
-        if (pick_force > 2) return -1;
+        if (pick_force > 2 || mutate < 0 || mutate > 4) return -1;
         rx_in_t in{iq, N_RX, S_in, fine_peak, cfo_rad, network_id, plcf_type, sync_rms, sm_mmse != 0};
         in.pick_force = pick_force;
         in.pick_stale = pick_stale != 0;
+        in.mutate = mutate;
         rx_out_t o;
         if (use_float)
             rx_packet<float>(to_cfg(cfg), q, in, o);
@@ -389,6 +393,16 @@ int oracle_rx_picks(const uint32_t* cfg, const uint32_t* psdef, uint32_t N_RX, c
         std::fprintf(stderr, "oracle_rx: %s\n", e.what());
         return -2;
     }
+}
+
+int oracle_rx_picks(const uint32_t* cfg, const uint32_t* psdef, uint32_t N_RX, const float* iq, uint32_t S_in,
+                    int64_t fine_peak, double cfo_rad, uint32_t network_id, uint32_t plcf_type, int16_t* pcc_llr,
+                    int16_t* pdc_llr, float* pcc_llr_f, float* pdc_llr_f, float* meta, int use_float,
+                    const float* sync_rms, int sm_mmse, int pick_force, int pick_stale, float* picks,
+                    uint32_t picks_cap, uint32_t* n_picks) {
+    return oracle_rx_mutant(cfg, psdef, N_RX, iq, S_in, fine_peak, cfo_rad, network_id, plcf_type, pcc_llr, pdc_llr,
+                            pcc_llr_f, pdc_llr_f, meta, use_float, sync_rms, sm_mmse, pick_force, pick_stale, picks,
+                            picks_cap, n_picks, 0);
 }
 
 int oracle_rx(const uint32_t* cfg, const uint32_t* psdef, uint32_t N_RX, const float* iq, uint32_t S_in,

@@ -454,20 +454,24 @@ struct rx_state_t {
         return s;
     }
 
+    // the derotation ramp's increment per subcarrier (rx_in_t::mutate 1: the opposite sign)
+    double ramp_inc() const { return in.mutate == 1 ? -sto_inc : sto_inc; }
+
     // rx_synced.cpp:748-771 (FFT, bin extraction, amplitude scaling, STO derotation)
     void fft_scale(const std::vector<std::vector<C>>& s, uint32_t CP, std::vector<std::vector<cd>>& dst) {
         const uint32_t Nd = dm.N_b_DFT_os, N = dm.N_b_OCC;
         auto& plan = get_plan<R>(Nd, -1);
         std::vector<C> f(Nd);
         const double scale = static_cast<double>(std::sqrt(static_cast<float>(N)) / static_cast<float>(Nd));
-        const double ph_start = -sto_inc * static_cast<double>(N / 2);
+        const double inc = ramp_inc();
+        const double ph_start = -inc * static_cast<double>(N / 2);
         for (uint32_t a = 0; a < N_RX; ++a) {
             plan.run(&s[a][CP], f.data());
             dst[a].assign(Nf, cd{0, 0});
             for (uint32_t j = 0; j <= N / 2; ++j) dst[a][N / 2 + j] = cd(f[j].real(), f[j].imag());
             for (uint32_t j = 0; j < N / 2; ++j) dst[a][j] = cd(f[dm.off_lower + j].real(), f[dm.off_lower + j].imag());
             for (uint32_t k = 0; k < Nf; ++k) {
-                const double ang = ph_start + sto_inc * static_cast<double>(k);
+                const double ang = ph_start + inc * static_cast<double>(k);
                 dst[a][k] *= scale * cd(std::cos(ang), std::sin(ang));
             }
         }
@@ -550,7 +554,7 @@ struct rx_state_t {
         // derotate the STF symbol and re-estimate (rx_synced.cpp:574-601)
         for (uint32_t a = 0; a < N_RX; ++a)
             for (uint32_t k = 0; k < Nf; ++k) {
-                const double ang = -sto_inc * static_cast<double>(dm.N_b_OCC / 2) + sto_inc * static_cast<double>(k);
+                const double ang = -ramp_inc() * static_cast<double>(dm.N_b_OCC / 2) + ramp_inc() * static_cast<double>(k);
                 Y[a][k] *= cd(std::cos(ang), std::sin(ang));
             }
         stf_zf(Y);
@@ -650,7 +654,7 @@ struct rx_state_t {
             return static_cast<uint32_t>(ret);
         };
         auto Hz = [&](uint32_t rx, uint32_t ts, uint32_t c) {
-            const cd v = zf[rx][ts][off + c * step];
+            const cd v = zf[rx][ts][off + (in.mutate == 4 ? 0 : c * step)];
             return cf(static_cast<float>(v.real()), static_cast<float>(v.imag()));
         };
         out.mimo_N_TS_other = NTS;
@@ -667,13 +671,23 @@ struct rx_state_t {
         for (uint32_t a = 0; a < N_RX; ++a)
             for (uint32_t t = t0; t <= ts_last; ++t) {
                 const uint32_t tl = (ps_idx % 2 == 1) ? ((t % 4) ^ 2) : (t % 4);
-                const auto& z = mode_lr ? zfi[a][t] : zf[a][t];
+                const std::vector<cd>* zp = mode_lr ? &zfi[a][t] : &zf[a][t];
+                std::vector<cd> held;
+                if (in.mutate == 3 && mode_lr) {  // the left symbol's pilots in the right symbol's slots too
+                    const uint32_t offl = (ps_idx % 2 == 0) ? ((t % 4) >= 2) : ((t % 4) < 2);  // drs_zf, lhs
+                    held = *zp;
+                    for (size_t i = 0; 2 * i + 1 < held.size(); ++i) held[2 * i + (1 - offl)] = held[2 * i + offl];
+                    zp = &held;
+                }
+                const auto& z = *zp;
+                const bool rev = in.mutate == 2;
                 auto& h = chest[a][t];
                 h.assign(Nf, cd{0, 0});
                 for (uint32_t f = 0; f < Nf; ++f) {
                     const uint32_t ip = L.pilot(rel, tl, f), iw = L.weight(rel, tl, f);
                     cd acc{0, 0};
-                    for (uint32_t i = 0; i < n; ++i) acc += z[ip + i] * static_cast<double>(L.weights[iw * n + i]);
+                    for (uint32_t i = 0; i < n; ++i)
+                        acc += z[ip + i] * static_cast<double>(L.weights[iw * n + (rev ? n - 1 - i : i)]);
                     h[f] = acc;
                 }
             }

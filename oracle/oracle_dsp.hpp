@@ -39,6 +39,12 @@ struct rx_in_t {  // sync_report_t subset + HARQ scrambling parameters
     // operation's pick (the first operation keeps its own)
     int pick_force = -1;
     bool pick_stale = false;
+    // test-only wrong receivers (tests/test_rx_selective_host.py: the selective windows must tell them from
+    // the right one). 0: none; 1: the STO derotation ramp with the opposite sign; 2: the Wiener weights of
+    // every interpolation window applied to its pilots in reversed order; 3: in lr mode the left DRS
+    // symbol's pilots stand in for the right one's as well (no interpolation in time); 4: the MIMO report reads
+    // its first wideband cell four times
+    int mutate = 0;
 };
 
 struct rx_out_t {

@@ -51,6 +51,7 @@ def lib():
                                 C.c_uint32, I16P, I16P, C.c_void_p, C.c_void_p, F32P, C.c_int, C.c_void_p, C.c_int]
         L.oracle_rx_picks.argtypes = L.oracle_rx.argtypes + [C.c_int, C.c_int, C.c_void_p, C.c_uint32,
                                                              C.POINTER(C.c_uint32)]
+        L.oracle_rx_mutant.argtypes = L.oracle_rx_picks.argtypes + [C.c_int]
         L.oracle_loopback_timed.argtypes = [U32P, U32P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32]
         L.oracle_loopback_timed.restype = C.c_double
         L.oracle_loopback_timed2.argtypes = [U32P, U32P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
@@ -123,13 +124,14 @@ def tx(cf, ps, pcc_d, pdc_d, S_slot, codebook=0, network_id=100, plcf_type=1, gi
 
 
 def rx(cf, ps, iq, fine_peak=0, cfo_rad=0.0, network_id=100, plcf_type=1, use_float=False, sync_rms=None,
-       sm_mmse=False, pick_force=None, pick_stale=False):
+       sm_mmse=False, pick_force=None, pick_stale=False, mutate=0):
     """iq: complex64 [N_RX, S_in]; sync_rms: the sync report's rms_array (8 floats, optional);
     sm_mmse: demodulate spatial multiplexing (N_SS > 1) by MMSE. Returns dict with int16/float LLRs
     and meta; r["lut_picks"] lists (profile, snr_dB_at_pick) of every DRS operation in order, the
     profile (0: -5 dB, 1: 15 dB, 2: 35 dB) being the one the SNR estimate selects.
     Test-only mutations of the pick: pick_force=p uses profile p at every DRS operation, pick_stale uses
-    the previous DRS operation's pick."""
+    the previous DRS operation's pick. mutate: a test-only wrong receiver (oracle_dsp.hpp rx_in_t::mutate: 1 the
+    STO ramp's sign, 2 the Wiener weights reversed, 3 the left DRS symbol held in lr mode, 4 the MIMO report's first wideband cell four times), 0 for none."""
     sz = packet_sizes(ps)
     iq = np.ascontiguousarray(iq, dtype=np.complex64)
     n_rx, s_in = iq.shape
@@ -141,11 +143,11 @@ def rx(cf, ps, iq, fine_peak=0, cfo_rad=0.0, network_id=100, plcf_type=1, use_fl
     srms = None if sync_rms is None else np.ascontiguousarray(np.resize(np.asarray(sync_rms, np.float32), 8))
     picks = np.zeros((64, 2), dtype=np.float32)
     n_picks = C.c_uint32()
-    r = lib().oracle_rx_picks(cf, ps, n_rx, iq.view(np.float32).reshape(-1), s_in, int(fine_peak), float(cfo_rad),
+    r = lib().oracle_rx_mutant(cf, ps, n_rx, iq.view(np.float32).reshape(-1), s_in, int(fine_peak), float(cfo_rad),
                               network_id, plcf_type, pcc, pdc, pccf.ctypes.data, pdcf.ctypes.data, meta,
                               int(use_float), srms.ctypes.data if srms is not None else None, int(sm_mmse),
                               -1 if pick_force is None else int(pick_force), int(pick_stale), picks.ctypes.data,
-                              len(picks), C.byref(n_picks))
+                              len(picks), C.byref(n_picks), int(mutate))
     assert r == 0, r
     assert n_picks.value <= len(picks), n_picks.value
     return dict(lut_picks=[(int(p), float(s)) for p, s in picks[: n_picks.value]],
