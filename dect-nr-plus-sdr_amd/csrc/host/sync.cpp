@@ -1,7 +1,7 @@
 // C-ABI synchronisation entry point (include/dnrp.h dnrp_rx_sync_batch): per-(u, b) tables built
 // as the sync_chunk_t / crosscorrelator_t / stf_template_t constructors do
 // (sync_chunk.cpp:32-123, crosscorrelator.cpp:22-59, stf_template.cpp:22-206), then three launches
-// (kernels/sync.hip).
+// (kernels/sync_steps.hip, sync_detect.hip, sync_fine.hip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -338,7 +338,7 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
     }
     a.fine_all = ctx->sync_fine_all;
     a.det_stage = dev::sync_detect_stage(a);
-    if (dev::sync_detect_lds(a) > 160 * 1024 || (16 + 2 * (size_t(1) << a.log2_fft)) * sizeof(float2) > 160 * 1024)
+    if (dev::sync_detect_lds(a) > 160 * 1024 || !dev::sync_fine_ok(a))
         return DNRP_EUNSUPPORTED;
     const size_t nsa = size_t(n) * a.n_ant * a.n_steps;
     if (!ctx->sy_P.ensure(nsa * sizeof(float)) || !ctx->sy_C.ensure(nsa * sizeof(float2)) ||

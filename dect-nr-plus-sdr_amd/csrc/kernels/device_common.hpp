@@ -83,6 +83,15 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void* p, uint32
                                              static_cast<int>(__builtin_amdgcn_readfirstlane(bytes)), 0x00020000);
 }
 
+// one float2 at byte offset off of a buffer descriptor (zero past its range). POLICY: the load's cache
+// policy bits (0: default, 2: nontemporal)
+template <int POLICY>
+__device__ __forceinline__ float2 buffer_load_f2(__amdgpu_buffer_rsrc_t rs, uint32_t off) {
+    typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+    const u2v v = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, POLICY);
+    return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
+}
+
 constexpr uint32_t ROW_SPAN_MAX = 1u << 28;  // float2 elements of a row behind a span descriptor (2 GiB)
 
 // stage_span_lo for one wavefront through a buffer descriptor: dst[i] = row[p0 + i], i in [0, n), zero

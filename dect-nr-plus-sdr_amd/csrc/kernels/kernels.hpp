@@ -492,7 +492,7 @@ struct chscan_args {
 };
 hipError_t launch_chscan(const chscan_args& a, uint32_t n_parts, hipStream_t st);
 
-// ---- synchronisation (sync.hip): sync_chunk_t::search() per window, reports in search order
+// ---- synchronisation (sync_steps.hip, sync_detect.hip, sync_fine.hip): sync_chunk_t::search() per window, reports in search order
 struct sync_res {  // layout of dnrp_sync_result (include/dnrp.h)
     uint32_t found, det_ant;
     float det_rms, det_metric;
@@ -585,6 +585,7 @@ bool sync_taps_match(const float* h, size_t n);  // compiled-in 9/10 sync taps =
 hipError_t launch_sync_post(const sync_args& a, uint32_t n, hipStream_t st);
 hipError_t launch_sync_beta(const sync_args& a, const sync_beta_args& ba, uint32_t n, hipStream_t st);
 hipError_t launch_sync_fine(const sync_args& a, uint32_t n, hipStream_t st);
+bool sync_fine_ok(const sync_args& a);  // the fine search's LDS fits (log2_fft)
 uint32_t sync_detect_stage(const sync_args& a);
 size_t sync_detect_lds(const sync_args& a);
 

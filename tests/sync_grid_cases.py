@@ -1,6 +1,6 @@
 """Inputs shared by tests/test_sync_grid_host.py and tests/test_gpu_sync_grid.py (TEST INFRASTRUCTURE):
 the sync geometry classes whose kernel forms are chosen by size inside a template instantiation
-(kernels/sync.hip launch_*: step = 4 b os_min, pattern, stf_len, D, n_uw, log2_fft), one case per class,
+(kernels/sync_*.hip launch_*: step = 4 b os_min, pattern, stf_len, D, n_uw, log2_fft), one case per class,
 and one window recipe for all of them.
 
 Every window: MCS 1 unless the case says otherwise, one random N_RX x N_TX mixing, a CFO within +-1.75

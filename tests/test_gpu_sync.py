@@ -1,4 +1,4 @@
-"""GPU synchronisation parity: dnrp_rx_sync_batch (kernels/sync.hip) against the oracle restatement
+"""GPU synchronisation parity: dnrp_rx_sync_batch (kernels/sync_*.hip) against the oracle restatement
 of sync_chunk_t::search() (oracle/oracle_sync.cpp) on identical windows.
 
 Tolerances: found flags, report count, detection antenna and time, N_eff_TX and the fine peak time
@@ -9,7 +9,7 @@ against the oracle RX started from the same (GPU) sync report (int16 LLRs within
 oracle's own search has found the same fine peak.
 
 Geometries: the bench configurations C2/C3/C4 (L/M 10/9, hl 24 stream kernel) plus every other sync
-kernel instantiation dispatched at kernels/sync.hip SYNC_DISPATCH / launch_sync_steps: L = M = 1
+kernel instantiation dispatched at kernels/sync_common.hpp sync_dispatch / launch_sync_steps: L = M = 1
 (<1,1,0>), 40/27 (<0,0,0>, generic taps), os_min 2 (<9,10,4>), two transmit streams, and eight
 antennas with the fourth STF template (N_eff_TX = 8, crosscorrelator.cpp:122-251,
 physical_resources.hpp:44); the wave-kernel fallback of the step sums (DNRP_SYNC_STREAM=0).

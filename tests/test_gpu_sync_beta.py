@@ -1,4 +1,4 @@
-"""Beta search of the synchronisation on the GPU (dnrp_ctx_set_sync_beta_search; kernels/sync.hip
+"""Beta search of the synchronisation on the GPU (dnrp_ctx_set_sync_beta_search; kernels/sync_fine.hip
 sync_beta_kernel, sync_beta_decide, the per-b template rows of sync_fine_kernel): packets of every
 b <= b_max in the stream of a b_max receiver, inputs of tests/sync_beta_cases.py (30 dB, MCS 1, random
 mixing, CFO within +-1.75 subcarriers; tests/test_sync_beta_host.py proves their margin to the threshold).

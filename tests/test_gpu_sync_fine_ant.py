@@ -1,5 +1,5 @@
 """Fine search over every antenna with a coarse peak on the GPU (dnrp_ctx_set_sync_fine_all_antennas,
-dnrp_rx_sync_fine_peaks; kernels/sync.hip sync_fine_ant_kernel, sync_fine_combine_kernel), inputs and the numpy
+dnrp_rx_sync_fine_peaks; kernels/sync_fine.hip sync_fine_ant_kernel, sync_fine_combine_kernel), inputs and the numpy
 restatement of tests/sync_fine_ant_cases.py (tests/test_sync_fine_ant_host.py proves the inputs' margins, which
 is what lets this file demand exact indices and an exact N_eff_TX).
 

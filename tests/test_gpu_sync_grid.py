@@ -1,4 +1,4 @@
-"""GPU synchronisation parity on the geometry classes that the launchers of kernels/sync.hip choose by
+"""GPU synchronisation parity on the geometry classes that the launchers of kernels/sync_*.hip choose by
 size inside a template instantiation (tests/sync_grid_cases.py; tests/test_sync_grid_host.py proves the
 inputs and the coverage): dnrp_rx_sync_batch against the oracle search on identical windows, with the
 tolerances of tests/test_gpu_sync.py (_compare, unchanged): counts, detection, N_eff_TX and the fine

@@ -29,7 +29,7 @@ def test_oracle_finds_every_packet(name):
 
 
 def _signature(name):
-    """the sizes the launchers of kernels/sync.hip choose by: resampler class (L, M, os_min), step, patterns,
+    """the sizes the launchers of kernels/sync_*.hip choose by: resampler class (L, M, os_min), step, patterns,
     fine FFT size, antennas"""
     g = G.sync_geometry(name)
     _, _, n_ant, os_min, L, M = G.CASES[name][1]
