@@ -341,6 +341,14 @@ struct dnrp_ctx {
     bool rx_sto_on = false;
     float rx_sto_gain = 1.0f;
     dbuf sto_sym;
+    // residual CFO tracking (dnrp_ctx_set_rx_cfo_tracking) likewise; cfo_sym: [slot][rx_nsym_cap + 1] mixer entry
+    // (phase a, increment) each symbol was mixed with; cfo_keep: the PCC phase's zero-forced DRS pilots
+    // [slot][RX_CFO_KEEP][N_RX][4][14 b_max], which the PDC phase's first pairs reach back to
+    uint32_t cfo_track_on = 0;
+    float cfo_track_gain = 1.0f;
+    bool rx_cfo_on = false;
+    float rx_cfo_gain = 1.0f;
+    dbuf cfo_sym, cfo_keep;
     // MIMO report options (dnrp_ctx_set_rx_mimo_report): the setting, read once per dnrp_rx_pdc_batch.
     // mimo_rows: one dnrp_mimo_detail per request of the latest PDC call that ran rx_mimo_detail_kernel, sized
     // like mimo_out; mimo_rows_m: that call's m where it ran with detail = 1, else 0 (dnrp_rx_mimo_detail)

@@ -189,8 +189,9 @@ enum class pdc_path {
 
 // every eligibility condition of the receivers, in order of preference. fa: the group's front-end
 // arguments (with the pilots zd where the front end writes them), ca: its cells arguments
-// sto_track: residual STO tracking is on (dnrp_ctx_set_rx_sto_tracking); the fused receiver and the grouped
-// Y path, the two measured-slower alternatives, do not take the per-symbol table and are never chosen then
+// sto_track: residual STO or CFO tracking is on (dnrp_ctx_set_rx_sto_tracking, dnrp_ctx_set_rx_cfo_tracking);
+// the fused receiver and the grouped Y path, the two measured-slower alternatives, do not take the per-symbol
+// tables and are never chosen then
 pdc_path choose_pdc_path(const switches& sw, const rx1_tables* t, const rx2_tables* t2, const dev::rx_front_args& fa,
                          const dev::rx_cells_args& ca, uint32_t ng, bool sto_track) {
     // both fused forms: the compile-time-tap wave front end and an instantiated (N_RX, N_eff_TX) pair
@@ -205,6 +206,8 @@ pdc_path choose_pdc_path(const switches& sw, const rx1_tables* t, const rx2_tabl
     if (!sto_track && sw.rx_group && ng > sw.rx_group && t2->q.N_DF_symb > t->pcc_max) return pdc_path::grouped_y;
     return pdc_path::plain_y;
 }
+
+bool rx_tracking(const dnrp_ctx* ctx) { return ctx->rx_sto_on || ctx->rx_cfo_on; }  // what the PCC call read
 
 // front end over a symbol list (the phase's DRS symbols) ahead of a fused receiver, or ahead of
 // rx_sto_track_kernel. The wave front ends take the device list; rx_fft_kernel works on runs of
@@ -254,12 +257,55 @@ int launch_sto_track(dnrp_ctx* ctx, const rx_phase& p, uint32_t sym_first, uint3
     return DNRP_OK;
 }
 
-// the PDC phase's part of residual STO tracking on the Y rows a DRS pass with the STF increment left; fa
-// then carries the table for the phase's launches
-int pdc_sto_track(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_front_args& fa, hipStream_t st) {
-    const int err = launch_sto_track(ctx, p, p.t->pcc_max + 1, t2->q.N_DF_symb, st);
-    fa.sto_sym = ctx->sto_sym.as<double>();
+// residual CFO tracking of one phase (rx_cfo_track_kernel) on the same rows, mixed with the STF values; fills
+// the mixer table entries of the symbols [sym_first, sym_last]
+int launch_cfo_track(dnrp_ctx* ctx, const rx_phase& p, uint32_t sym_first, uint32_t sym_last, hipStream_t st) {
+    const rx1_tables* t = p.t;
+    if (t->bplan.n_dops > dev::RX_CFO_KEEP) return DNRP_EUNSUPPORTED;  // the PCC phase's pilots kept for the PDC phase
+    dev::rx_cfo_args a{};
+    a.N_RX = ctx->cfg.N_TX_max;
+    a.Nf_pad = ctx->rx_Nf_pad;
+    a.n_sym_total = ctx->rx_nsym_cap + 1;
+    a.n_drs = t->N_occ / 4;
+    a.n_dops = p.plan->n_dops;
+    a.is_pdc = p.pdc;
+    a.sym_first = sym_first;
+    a.sym_last = sym_last;
+    a.n_stf = t->STF_CP + t->Nd;
+    a.sym_len = t->CP + t->Nd;
+    a.Nd = t->Nd;
+    a.gain = ctx->rx_cfo_gain;
+    a.dl = p.plan->dl.as<uint32_t>();
+    a.dmeta = p.plan->dmeta.as<uint32_t>();
+    a.drs_k = t->drs_k.as<uint32_t>();
+    a.drs_v = t->drs_v.as<float>();
+    a.Y = ctx->Y.as<float2>();
+    a.pin = ctx->rx_in.as<dev::rx_pkt_in>();
+    a.st = ctx->rx_st.as<dev::rx_pkt_state>();
+    a.sel = p.sel;
+    a.tab = ctx->cfo_sym.as<double2>();
+    a.keep = ctx->cfo_keep.as<float2>();
+    ctx->tic("rx_cfo_track", st);
+    if (dev::launch_rx_cfo_track(a, p.n, st) != hipSuccess) return DNRP_EDEVICE;
+    ctx->toc("rx_cfo_track", st);
+    return DNRP_OK;
+}
+
+// the trackers that are on, over one phase's symbols, on the Y rows a DRS pass with the STF values left (one
+// pass for both: each measures the same rows); fa then carries their tables for the phase's launches
+int launch_track(dnrp_ctx* ctx, const rx_phase& p, uint32_t sym_first, uint32_t sym_last, dev::rx_front_args& fa,
+                 hipStream_t st) {
+    int err = DNRP_OK;
+    if (ctx->rx_sto_on) err = launch_sto_track(ctx, p, sym_first, sym_last, st);
+    if (err == DNRP_OK && ctx->rx_cfo_on) err = launch_cfo_track(ctx, p, sym_first, sym_last, st);
+    if (ctx->rx_sto_on) fa.sto_sym = ctx->sto_sym.as<double>();
+    if (ctx->rx_cfo_on) fa.cfo_sym = ctx->cfo_sym.as<double2>();
     return err;
+}
+
+// the PDC phase's part of residual STO / CFO tracking
+int pdc_track(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_front_args& fa, hipStream_t st) {
+    return launch_track(ctx, p, p.t->pcc_max + 1, t2->q.N_DF_symb, fa, st);
 }
 
 // the phase's DRS symbols first (pilots, SNR sums; their bins to Y only where they carry PDC cells),
@@ -293,13 +339,13 @@ int pdc_fused(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_fr
 
 // DRS pass (the phase's DRS symbols: pilots in Y, SNR sums), the SNR chain's LUT picks, then one
 // workgroup per (packet, epoch): front end of the epoch's symbols + equaliser, on the twin plan where
-// the phase has one. With residual STO tracking the DRS pass feeds rx_sto_track_kernel and is repeated
-// with its table, which the epoch kernel's front end takes too
+// the phase has one. With residual STO / CFO tracking the DRS pass feeds the tracking kernels and is repeated
+// with their tables, which the epoch kernel's front end takes too
 int pdc_epoch(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_front_args fa,
               const dev::rx_cells_args& ca, hipStream_t st) {
     int err = launch_fft_list(ctx, fa, t2->ep_drs.as<uint16_t>(), t2->n_ep_drs, p.n, st);
-    if (err == DNRP_OK && ctx->rx_sto_on) {
-        err = pdc_sto_track(ctx, p, t2, fa, st);
+    if (err == DNRP_OK && rx_tracking(ctx)) {
+        err = pdc_track(ctx, p, t2, fa, st);
         if (err == DNRP_OK) err = launch_fft_list(ctx, fa, t2->ep_drs.as<uint16_t>(), t2->n_ep_drs, p.n, st);
     }
     if (err == DNRP_OK) err = launch_snr_chain(ctx, p, st);
@@ -357,10 +403,10 @@ int pdc_grouped_y(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::r
 int pdc_plain_y(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_front_args fa,
                 const dev::rx_cells_args& ca, hipStream_t st) {
     if (t2->q.N_DF_symb > p.t->pcc_max) {
-        if (ctx->rx_sto_on) {  // the phase's DRS symbols (the plan's ops behind the PCC phase's) first
+        if (rx_tracking(ctx)) {  // the phase's DRS symbols (the plan's ops behind the PCC phase's) first
             const uint32_t d0 = p.t->bplan.n_dops, nd = p.plan->n_dops - d0;
             int err = launch_fft_list(ctx, fa, p.plan->dl16.as<uint16_t>() + d0, nd, p.n, st, p.plan->dl_h.data() + d0);
-            if (err == DNRP_OK) err = pdc_sto_track(ctx, p, t2, fa, st);
+            if (err == DNRP_OK) err = pdc_track(ctx, p, t2, fa, st);
             if (err != DNRP_OK) return err;
         }
         fa.sym_count = t2->q.N_DF_symb - p.t->pcc_max;
@@ -447,8 +493,8 @@ int pdc_group(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const floa
               hipStream_t st) {
     auto fa = front_args(ctx, p.t, iq_in, p.sel, snr_from_front(ctx, p.t) ? p.plan : nullptr);
     const auto ca = cells_args(ctx, p);
-    const pdc_path path = choose_pdc_path(ctx->sw, p.t, t2, fa, ca, p.n, ctx->rx_sto_on);
-    if (ctx->rx_sto_on) {  // the PCC plan's ops are the PDC plan's ops up to pcc_max: the state continues there
+    const pdc_path path = choose_pdc_path(ctx->sw, p.t, t2, fa, ca, p.n, rx_tracking(ctx));
+    if (rx_tracking(ctx)) {  // the PCC plan's ops are the PDC plan's ops up to pcc_max: the state continues there
         uint32_t d0 = 0;
         while (d0 < p.plan->n_dops && p.plan->dl_h[d0] <= p.t->pcc_max) ++d0;
         if (d0 != p.t->bplan.n_dops) return DNRP_EUNSUPPORTED;
@@ -551,6 +597,14 @@ int dnrp_rx_pcc_batch(dnrp_ctx* ctx, uint32_t n, const dnrp_sync_report* sr, con
         if (!ctx->sto_sym.ensure(tbytes)) return DNRP_ENOMEM;
         HIPCHK(hipMemsetAsync(ctx->sto_sym.p, 0xFF, tbytes, st));
     }
+    ctx->rx_cfo_on = ctx->cfo_track_on != 0;  // and the residual CFO tracking setting
+    ctx->rx_cfo_gain = ctx->cfo_track_gain;
+    if (ctx->rx_cfo_on) {  // its table likewise, and the PCC phase's pilots
+        const size_t tbytes = size_t(n) * (ctx->rx_nsym_cap + 1) * sizeof(double2);
+        const size_t kbytes = size_t(n) * dev::RX_CFO_KEEP * ctx->cfg.N_TX_max * 14 * ctx->cfg.b_max * 4 * sizeof(float2);
+        if (!ctx->cfo_sym.ensure(tbytes) || !ctx->cfo_keep.ensure(kbytes)) return DNRP_ENOMEM;
+        HIPCHK(hipMemsetAsync(ctx->cfo_sym.p, 0xFF, tbytes, st));
+    }
     {
         // zero-forced DRS pilots of every slot (the fused receiver's only): at most one DRS symbol per
         // 5 symbols (N_eff_TX <= 4) plus the zero op
@@ -602,16 +656,15 @@ int dnrp_rx_pcc_batch(dnrp_ctx* ctx, uint32_t n, const dnrp_sync_report* sr, con
         fa.sym_first = 1;
         fa.sym_count = t->pcc_max;
         const rx_phase p{t, &t->bplan, ng, gsel, false, 2, t->pcc_k.as<uint32_t>(), t->pcc_sym.as<uint16_t>(), pcc_llr, 196, false};
-        // residual STO tracking: the phase's few symbols with the STF increment, the table from their DRS
-        // rows, then the same launch again with the table
-        for (int pass = ctx->rx_sto_on ? 0 : 1; pass < 2; ++pass) {
+        // residual STO / CFO tracking: the phase's few symbols with the STF values, the tables from their DRS
+        // rows, then the same launch again with the tables
+        for (int pass = rx_tracking(ctx) ? 0 : 1; pass < 2; ++pass) {
             ctx->tic("rx_fft_pcc", st);
             if (dev::launch_rx_fft(fa, ng, st) != hipSuccess) return DNRP_EDEVICE;
             ctx->toc("rx_fft_pcc", st);
             if (pass) break;
-            err = launch_sto_track(ctx, p, 0, t->pcc_max, st);
+            err = launch_track(ctx, p, 0, t->pcc_max, fa, st);
             if (err != DNRP_OK) return err;
-            fa.sto_sym = ctx->sto_sym.as<double>();
         }
         const auto ca = cells_args(ctx, p);
         err = launch_back(ctx, p, &ca, st);
@@ -675,7 +728,7 @@ int dnrp_rx_pdc_batch(dnrp_ctx* ctx, uint32_t m, const dnrp_pdc_req* req, const 
         rx2_tables* t2 = get_rx2(ctx, d, &err);
         if (!t2) return err;
         if (d.u != t->u || d.b != t->b || t2->q.N_eff_TX != t->N_eff_TX) return DNRP_EINVAL;
-        if (ctx->rx_sto_on && t2->sm) return DNRP_EUNSUPPORTED;  // the MMSE receiver has no tracking; nothing launched yet
+        if (rx_tracking(ctx) && t2->sm) return DNRP_EUNSUPPORTED;  // the MMSE receiver has no tracking; nothing launched yet
         if (llr_stride < t2->q.G) return DNRP_EINVAL;
         for (uint32_t r : g.second) {
             if (t2->q.N_DF_symb > ctx->rx_slot_cap[req[r].pcc_index]) return DNRP_EINVAL;
@@ -766,6 +819,39 @@ int dnrp_rx_sto_track(dnrp_ctx* ctx, uint32_t n_slots, double* inc, uint32_t n_s
     (void)hipSetDevice(ctx->cfg.device);
     HIPCHK(hipMemcpyAsync(inc, ctx->sto_sym.p, size_t(n_slots) * *n_sym * sizeof(double), hipMemcpyDeviceToHost,
                           static_cast<hipStream_t>(stream)));
+    return DNRP_OK;
+}
+
+int dnrp_ctx_set_rx_cfo_tracking(dnrp_ctx* ctx, uint32_t on, float gain) {
+    if (!ctx || on > 1 || !std::isfinite(gain) || gain < 0.0f || gain > 1.0f) return DNRP_EINVAL;
+    ctx->cfo_track_on = on;
+    ctx->cfo_track_gain = gain;
+    return DNRP_OK;
+}
+
+int dnrp_ctx_get_rx_cfo_tracking(const dnrp_ctx* ctx, uint32_t* on, float* gain) {
+    if (!ctx) return DNRP_EINVAL;
+    if (on) *on = ctx->cfo_track_on;
+    if (gain) *gain = ctx->cfo_track_gain;
+    return DNRP_OK;
+}
+
+int dnrp_rx_cfo_track(dnrp_ctx* ctx, uint32_t n_slots, double* inc, double* phase, uint32_t n_sym_cap, uint32_t* n_sym,
+                      void* stream) {
+    if (!ctx || !n_sym || !ctx->rx_valid || !ctx->rx_cfo_on) return DNRP_EINVAL;
+    *n_sym = ctx->rx_nsym_cap + 1;
+    if (!inc && !phase) return DNRP_OK;  // size query
+    if (n_slots == 0 || n_slots > ctx->rx_n || n_sym_cap < *n_sym) return DNRP_EINVAL;
+    (void)hipSetDevice(ctx->cfg.device);
+    // the device table holds (phase, increment) pairs: one strided copy per output array
+    const size_t rows = size_t(n_slots) * *n_sym;
+    const auto* src = static_cast<const char*>(ctx->cfo_sym.p);
+    if (phase)
+        HIPCHK(hipMemcpy2DAsync(phase, sizeof(double), src, sizeof(double2), sizeof(double), rows, hipMemcpyDeviceToHost,
+                                static_cast<hipStream_t>(stream)));
+    if (inc)
+        HIPCHK(hipMemcpy2DAsync(inc, sizeof(double), src + sizeof(double), sizeof(double2), sizeof(double), rows,
+                                hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));
     return DNRP_OK;
 }
 

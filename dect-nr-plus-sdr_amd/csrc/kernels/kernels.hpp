@@ -139,6 +139,11 @@ struct rx_pkt_state {       // written by rx_stf_kernel, read by the later RX ke
     // the number of those ops, where the PDC phase continues; rx_stf_kernel starts them at (sto_inc, 0)
     double sto_run;
     uint32_t sto_ops, pad0;
+    // residual CFO tracking (rx_cfo_track_kernel): the running mixer entry (phase a, increment) after the PCC
+    // phase's DRS ops and the number of those ops, where the PDC phase continues; rx_stf_kernel starts them
+    // at (n_stf inc0, inc1, 0)
+    double cfo_a, cfo_run;
+    uint32_t cfo_ops, pad1;
 };
 
 struct rx_front_args {
@@ -193,6 +198,10 @@ struct rx_front_args {
     // residual STO tracking (rx_sto_track_kernel's table): symbol l of a slot is derotated with
     // sto_sym[slot n_sym_total + l] instead of the packet's rx_pkt_state::sto_inc; null: sto_inc
     const double* sto_sym;
+    // residual CFO tracking (rx_cfo_track_kernel's table): DECT-rate sample m of symbol l of a slot is mixed
+    // with the phase a + (m - n_stf) inc, (a, inc) = cfo_sym[slot n_sym_total + l], instead of the packet's
+    // (n_stf inc0, inc1); null: those
+    const double2* cfo_sym;
 };
 bool rx_fft_wave_path(const rx_front_args& a);  // launch_rx_fft takes rx_fft_wave_kernel (snr_part supported)
 hipError_t launch_rx_stf(const rx_front_args& a, uint32_t n, hipStream_t st);
@@ -249,6 +258,29 @@ struct rx_sto_args {
     double* tab;            // [slot][n_sym_total]
 };
 hipError_t launch_rx_sto_track(const rx_sto_args& a, uint32_t n, hipStream_t st);
+
+// Residual CFO from the DRS symbols (the intent of RX_SYNCED_PARAM_CFO_RESIDUAL_BASED_ON_DRS,
+// rx_synced_param.hpp:162-181), one WG per packet: the phase plan's DRS ops in order, each compared with the
+// latest earlier op of the same stream set on Y rows the front end mixed with the STF values alone, and the
+// per-symbol mixer table the front ends then take (rx_front_args::cfo_sym)
+constexpr uint32_t RX_CFO_KEEP = 2;  // PCC-phase DRS ops whose pilots are kept for the PDC phase's first pairs
+struct rx_cfo_args {
+    uint32_t N_RX, Nf_pad, n_sym_total, n_drs, n_dops, is_pdc;
+    uint32_t sym_first, sym_last;  // the phase's symbols: the table entries it fills (the PCC phase from the STF, 0)
+    uint32_t n_stf, sym_len, Nd;   // STF_CP + N_b_DFT_os, CP + N_b_DFT_os, N_b_DFT_os (DECT-rate samples)
+    double gain;            // scales each residual before it is taken off the running increment
+    const uint32_t* dl;     // the phase plan's DRS ops (rx_snr_args)
+    const uint32_t* dmeta;
+    const uint32_t* drs_k;
+    const float* drs_v;
+    const float2* Y;
+    const rx_pkt_in* pin;
+    rx_pkt_state* st;
+    const uint32_t* sel;    // launch packet -> slot / output row
+    double2* tab;           // [slot][n_sym_total]
+    float2* keep;           // [slot][RX_CFO_KEEP][N_RX][4][n_drs]: zero-forced pilots of the PCC phase's ops
+};
+hipError_t launch_rx_cfo_track(const rx_cfo_args& a, uint32_t n, hipStream_t st);
 
 struct rx_lut {             // one Wiener LUT: [T][4][Nf] pilot | weight << 16, weights [n_vec][n]
     const uint32_t* pw;

@@ -363,6 +363,9 @@ __global__ void __launch_bounds__(256) rx_stf_kernel(rx_front_args A) {
     inc /= static_cast<double>(A.N_RX);
     S.sto_inc = S.sto_run = inc;  // residual STO tracking starts from the STF estimate (rx_sto_track_kernel)
     S.sto_ops = S.pad0 = 0;
+    S.cfo_a = static_cast<double>(n_stf) * in.inc0;  // residual CFO tracking likewise (rx_cfo_track_kernel)
+    S.cfo_run = S.inc1;
+    S.cfo_ops = S.pad1 = 0;
     S.sto_frac = static_cast<float>(atan2(sin(inc), cos(inc)) / 2.0 / 3.14159265358979323846 * Nd);
     // STF SNR on the derotated symbol (estimator_snr.cpp:48-66,104-146)
     double sn = 0.0, nn = 0.0;
@@ -399,8 +402,9 @@ __host__ __device__ inline uint32_t rx_in_cap(uint32_t Nd, uint32_t CP, uint32_t
     return ((pass * (Nd + CP)) * M + L - 1) / L + W + 2 * M + 2 * L;
 }
 
-// TRK: residual STO tracking (A.sto_sym set), every symbol derotated with its own table entry instead of
-// rot[]; an instantiation of its own, so the default one keeps its registers (64 VGPRs: 8 waves per SIMD)
+// TRK: residual STO / CFO tracking (A.sto_sym or A.cfo_sym set), every symbol derotated with its own STO table
+// entry instead of rot[] and mixed with its own CFO table entry (rx_cfo_of) instead of the packet's STF
+// values; an instantiation of its own, so the default one keeps its registers (64 VGPRs: 8 waves per SIMD)
 template <int LR, int MR, int HLR, bool TRK = false>
 __global__ void __launch_bounds__(RX_THREADS) rx_fft_kernel(rx_front_args A) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
@@ -456,13 +460,20 @@ __global__ void __launch_bounds__(RX_THREADS) rx_fft_kernel(rx_front_args A) {
                 if (mb + LR <= m0 || mb >= m0 + static_cast<int>(Nd)) continue;
                 float2 y[LR];
                 PB::run(inbuf + MR * (q - qb0), taps, y);
-                float2 r = phasor(phi_stf + static_cast<double>(mb - static_cast<int>(n_stf)) * S.inc1);
+                float2 r, stp = step1;
+                if constexpr (TRK) {  // the symbol's own mixer entry, the same expression
+                    const double2 mix = rx_cfo_of(A, in, S, n_stf, pkt, lp + s);
+                    r = phasor(mix.x + static_cast<double>(mb - static_cast<int>(n_stf)) * mix.y);
+                    stp = phasor(mix.y);
+                } else {
+                    r = phasor(phi_stf + static_cast<double>(mb - static_cast<int>(n_stf)) * S.inc1);
+                }
                 float2* dst = fa + s * Nd;
 #pragma unroll
                 for (int k = 0; k < LR; ++k) {
                     const uint32_t idx = static_cast<uint32_t>(mb + k - m0);
                     if (idx < Nd) dst[idx] = cmul(y[k], r);
-                    r = cmul(r, step1);
+                    r = cmul(r, stp);
                 }
             }
             __syncthreads();
@@ -470,8 +481,14 @@ __global__ void __launch_bounds__(RX_THREADS) rx_fft_kernel(rx_front_args A) {
             for (uint32_t s = 0; s < ns; ++s) {
                 const uint32_t l = lp + s;
                 const uint64_t m0 = n_stf + uint64_t(l - 1) * (A.CP + Nd) + A.CP;
-                resample_block<-1>(A, x, in.fine_peak, m0, Nd, inbuf, fa + s * Nd, taps,
-                                   phi_stf + static_cast<double>(m0 - n_stf) * S.inc1, S.inc1);
+                if constexpr (TRK) {
+                    const double2 mix = rx_cfo_of(A, in, S, n_stf, pkt, l);
+                    resample_block<-1>(A, x, in.fine_peak, m0, Nd, inbuf, fa + s * Nd, taps,
+                                       mix.x + static_cast<double>(m0 - n_stf) * mix.y, mix.y);
+                } else {
+                    resample_block<-1>(A, x, in.fine_peak, m0, Nd, inbuf, fa + s * Nd, taps,
+                                       phi_stf + static_cast<double>(m0 - n_stf) * S.inc1, S.inc1);
+                }
             }
         }
         const float2* F = fft_any<-1>(fa, fb, tw, A.plan, ns);
@@ -481,7 +498,7 @@ __global__ void __launch_bounds__(RX_THREADS) rx_fft_kernel(rx_front_args A) {
             extract_bins(A, F + s * Nd, &v, k);
             float2 r = rot[k];
             if constexpr (TRK) {  // the symbol's own increment, rot[]'s expression per bin
-                const double si = A.sto_sym[size_t(pkt) * A.n_sym_total + lp + s];
+                const double si = A.sto_sym ? A.sto_sym[size_t(pkt) * A.n_sym_total + lp + s] : S.sto_inc;
                 r = sto_rot(si, N, k);
             }
             A.Y[((size_t(pkt) * A.N_RX + a) * A.n_sym_total + lp + s) * A.Nf_pad + k] = cmul(v, r);
@@ -596,7 +613,7 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
     float2* Yrow = A.Y + ((size_t(pkt) * A.N_RX + a) * A.n_sym_total + l) * A.Nf_pad;
     const bool drs = so != 0xFFFFu;
     if constexpr (CT) {
-        rx_resample_ct<LR, MR, HLR>(A, in, S, sp, R, lane);
+        rx_resample_ct<LR, MR, HLR>(A, rx_cfo_of(A, in, S, A.STF_CP + Nd, pkt, l), sp, R, lane);
         // one instantiation of the (large, unrolled) FFT for both kinds of symbol: instruction cache
         const bool to_y = !A.no_y;
         rx_fft_bins<RT>(A, rx_sto_of(A, S, pkt, l), R, lane, [&](uint32_t k, float2 v) {
@@ -611,8 +628,9 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
     } else {
         constexpr int BR = (Nd + 2 * LR) / LR / 64 + 1;  // block rounds per lane
         const int n_stf = static_cast<int>(A.STF_CP + Nd);
-        const double phi_stf = static_cast<double>(n_stf) * in.inc0;  // mixer phase at the first data sample
-        const float2 step1 = phasor(S.inc1);
+        const double2 mix = rx_cfo_of(A, in, S, A.STF_CP + Nd, pkt, l);
+        const double phi_stf = mix.x;  // mixer phase at the first data sample
+        const float2 step1 = phasor(mix.y);
         float2 ys[BR][LR];
         // all rounds of the lane in one pass over the tap rows (pp_block::run_multi); rounds past
         // the symbol's last block read a valid window and are discarded
@@ -626,7 +644,7 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
             const int q = sp.qb0 + static_cast<int>(lane) + 64 * rd;
             if (q < sp.qb1) {
                 const int mb = static_cast<int>(A.m_star) + LR * q;
-                float2 r = phasor(phi_stf + static_cast<double>(mb - n_stf) * S.inc1);
+                float2 r = phasor(phi_stf + static_cast<double>(mb - n_stf) * mix.y);
 #pragma unroll
                 for (int k = 0; k < LR; ++k) {
                     const uint32_t idx = static_cast<uint32_t>(mb + k - sp.m0);
@@ -714,7 +732,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) rx
         const __amdgpu_buffer_rsrc_t yr =
             row_rsrc(A.Y + ((size_t(pkt) * A.N_RX + a) * A.n_sym_total + l) * A.Nf_pad, to_y ? A.Nf_pad * 8u : 0u);
         const bool drs = so != 0xFFFFu;
-        if constexpr (!experiment(XS_FE_SKIP_FIR)) rx_resample_ct<LR, MR, HLR>(A, in, S, sp, R, lane);
+        if constexpr (!experiment(XS_FE_SKIP_FIR)) rx_resample_ct<LR, MR, HLR>(A, rx_cfo_of(A, in, S, A.STF_CP + 1024, pkt, l), sp, R, lane);
         rx_fft_bins<true>(A, rx_sto_of(A, S, pkt, l), R, lane, [&](uint32_t k, float2 v) {
             // Y is written once and read by the next launch: nontemporal stores when that launch
             // comes after the whole batch, plain ones when it follows within a cache-sized group
@@ -796,11 +814,11 @@ hipError_t launch_rx_fft(const rx_front_args& a_in, uint32_t n, hipStream_t st) 
             hipLaunchKernelGGL((rx_fft_wave_kernel<9, 10, 24, false>), g, b, lds, st, a);
         }
     } else if (a.L == 9 && a.M == 10 && a.hl == 24)  // os_min 1 (225 taps)
-        a.sto_sym ? fast(rx_fft_kernel<9, 10, 24, true>) : fast(rx_fft_kernel<9, 10, 24>);
+        (a.sto_sym || a.cfo_sym) ? fast(rx_fft_kernel<9, 10, 24, true>) : fast(rx_fft_kernel<9, 10, 24>);
     else if (a.L == 9 && a.M == 10 && a.hl == 4)  // os_min 2
-        a.sto_sym ? fast(rx_fft_kernel<9, 10, 4, true>) : fast(rx_fft_kernel<9, 10, 4>);
+        (a.sto_sym || a.cfo_sym) ? fast(rx_fft_kernel<9, 10, 4, true>) : fast(rx_fft_kernel<9, 10, 4>);
     else
-        a.sto_sym ? fast(rx_fft_kernel<0, 0, 0, true>) : fast(rx_fft_kernel<0, 0, 0>);
+        (a.sto_sym || a.cfo_sym) ? fast(rx_fft_kernel<0, 0, 0, true>) : fast(rx_fft_kernel<0, 0, 0>);
     return hipGetLastError();
 }
 

@@ -7,6 +7,9 @@
 //  rx_sto_track_kernel  one WG per packet, only with residual STO tracking on: the STO increment after
 //                   every DRS symbol of the phase and the per-symbol table the front ends derotate with
 //                   (estimator_sto.cpp:64-97, 148-171).
+//  rx_cfo_track_kernel  one WG per packet, only with residual CFO tracking on: the mixer increment after
+//                   every DRS symbol of the phase, from the rotation between DRS symbols one period apart,
+//                   and the per-symbol table the front ends mix with (rx_synced_param.hpp:162-181).
 //  rx_cells_kernel  one WG per (packet, epoch): an epoch is a run of cell work over which the
 //                   interlaced pilot buffer (channel_antenna.hpp:38-63) does not change. The WG
 //                   rebuilds that buffer in LDS from the zero-forced DRS cells of Y, then every
@@ -240,6 +243,136 @@ __global__ void __launch_bounds__(STO_THREADS) rx_sto_track_kernel(rx_sto_args A
 hipError_t launch_rx_sto_track(const rx_sto_args& a, uint32_t n, hipStream_t st) {
     if (a.N_RX > 8 || a.n_dops > MAX_DOPS || a.sym_last >= a.n_sym_total || a.sym_first > a.sym_last) return hipErrorInvalidValue;
     hipLaunchKernelGGL(rx_sto_track_kernel, dim3(n), dim3(STO_THREADS), 0, st, a);
+    return hipGetLastError();
+}
+
+// ===================================================================== residual CFO tracking
+// What the reference's RX_SYNCED_PARAM_CFO_RESIDUAL_BASED_ON_DRS header describes (rx_synced_param.hpp:162-181:
+// two OFDM symbols with DRS cells are compared, N_step apart) and its stub does not compute
+// (estimator_cfo.cpp:65-74 multiplies neighbouring cells of one symbol). DRS op d at symbol l is compared with
+// d', the latest earlier op with the same first stream, at symbol l'. Both rows are in Y mixed with the STF
+// values alone. Consecutive DRS symbols of a stream are interlaced two subcarriers apart, so pilot i of d is
+// paired with the pilots of d' on either side of it: a timing offset turns the two products by opposite
+// angles, which cancel to first order in their sum. C sums h_d conj(h_d') over both pairs, the streams
+// TS_first..TS_last and the RX antennas as one complex number (estimator_cfo.cpp:41-53): one wavefront per
+// (antenna, stream), products in float, sums per lane and across lanes in double, the (antenna, stream) sums
+// added in index order by every thread. theta = wrap(atan2(C) + Psi(l) - Psi(l')) is the rotation the table
+// has not removed yet, Psi(l) = table phase - STF phase at the centre of symbol l's transform window; the
+// running increment loses gain theta / ((l - l') (CP + N_b_DFT_os)) and the phase stays continuous at the
+// first CP sample of symbol l + 1 (mixer.cpp adjust_phase_increment leaves the accumulated phase alone).
+// The PCC phase's ops leave their pilots in `keep`: the PDC phase's first pairs reach back to them, and by
+// then the front end has written those Y rows again with the table.
+constexpr uint32_t CFO_THREADS = 256;
+constexpr uint32_t CFO_TS = 4;  // streams of one DRS op (drs.cpp:90-127)
+
+__global__ void __launch_bounds__(CFO_THREADS) rx_cfo_track_kernel(rx_cfo_args A) {
+    __shared__ double cr[8 * CFO_TS], ci[8 * CFO_TS];  // per (rx, stream) of the op
+    __shared__ double psi[MAX_DOPS];                    // Psi at every op's symbol
+    const uint32_t pkt = rx_slot_of(A.sel, blockIdx.x), nd = A.n_drs;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, nw = CFO_THREADS / 64;
+    const size_t ast = size_t(A.n_sym_total) * A.Nf_pad, kst = size_t(A.N_RX) * CFO_TS * nd;
+    const float2* Yp = A.Y + size_t(pkt) * A.N_RX * ast;
+    float2* keep = A.keep + size_t(pkt) * RX_CFO_KEEP * kst;
+    double2* tab = A.tab + size_t(pkt) * A.n_sym_total;
+    rx_pkt_state* st = A.st + pkt;
+    const double inc1 = st->inc1, a0 = static_cast<double>(A.n_stf) * A.pin[pkt].inc0;
+    auto psi_of = [&](uint32_t l, double a, double inc) {
+        return (a - a0) + static_cast<double>((l - 1) * A.sym_len + (A.sym_len - A.Nd) + A.Nd / 2) * (inc - inc1);
+    };
+    // the PDC phase continues where the PCC phase stopped (and leaves that state as it is: a second PDC
+    // call on the same PCC batch starts from it again); every thread carries the same recurrence
+    double a = A.is_pdc ? st->cfo_a : a0, run = A.is_pdc ? st->cfo_run : inc1;
+    const uint32_t d_first = A.is_pdc ? min(st->cfo_ops, A.n_dops) : 0u;
+    for (uint32_t e = threadIdx.x; e < d_first; e += CFO_THREADS) {  // the PCC phase's ops from its table entries
+        const double2 t = tab[A.dl[e]];
+        psi[e] = psi_of(A.dl[e], t.x, t.y);
+    }
+    __syncthreads();
+    uint32_t d = d_first, lf = A.sym_first;
+    for (; d < A.n_dops; ++d) {
+        const uint32_t l = A.dl[d], meta = A.dmeta[d];
+        if (l > A.sym_last) break;
+        // a DRS symbol itself is mixed with the entry from before its own update
+        for (uint32_t s = lf + threadIdx.x; s <= l; s += CFO_THREADS) tab[s] = make_double2(a, run);
+        lf = max(lf, l + 1);
+        const uint32_t tf = meta & 0xFFu, tl = min((meta >> 8) & 0xFFu, tf + CFO_TS - 1), par = (meta >> 16) & 0xFFu;
+        const uint32_t nts = tl >= tf ? tl - tf + 1 : 0u, cnt = A.N_RX * nts;
+        int dp = -1;  // the latest earlier op of the same stream set
+        for (uint32_t e = d; e-- > 0;)
+            if ((A.dmeta[e] & 0xFFu) == tf) {
+                dp = static_cast<int>(e);
+                break;
+            }
+        const bool kept = dp >= 0 && static_cast<uint32_t>(dp) < d_first;  // its pilots come from `keep`
+        if (kept && dp >= static_cast<int>(RX_CFO_KEEP)) dp = -1;
+        const bool save = !A.is_pdc && d < RX_CFO_KEEP;
+        const double psi_d = psi_of(l, a, run);
+        if (threadIdx.x == 0) psi[d] = psi_d;
+        const uint32_t lp = dp >= 0 ? A.dl[dp] : 0u, parp = dp >= 0 ? (A.dmeta[dp] >> 16) & 0xFFu : 0u;
+        const float2* rows = Yp + size_t(l) * A.Nf_pad;
+        const float2* rowp = Yp + size_t(lp) * A.Nf_pad;
+        for (uint32_t p = wave; p < cnt && (save || dp >= 0); p += nw) {
+            const uint32_t ar = p / nts, tt = p % nts, t = tf + tt;
+            const uint32_t* __restrict__ kb = A.drs_k + (par * 4 + (t & 3u)) * nd;
+            const uint32_t* __restrict__ kp = A.drs_k + (parp * 4 + (t & 3u)) * nd;
+            const float* __restrict__ vv = A.drs_v + t * nd;
+            // the cell of d' on the other side of cell i: i - 1 where its cell i lies above, i + 1 where below
+            const int sh = kp[0] > kb[0] ? -1 : kp[0] < kb[0] ? 1 : 0;
+            const float2* kprow = keep + size_t(kept ? dp : 0) * kst + (size_t(ar) * CFO_TS + tt) * nd;
+            auto prev = [&](uint32_t i) {
+                return kept ? kprow[i] : cscale(rowp[ar * ast + kp[i]], vv[i]);
+            };
+            double br = 0.0, bi = 0.0;
+            for (uint32_t i = lane; i < nd; i += 64) {
+                const float2 h = cscale(rows[ar * ast + kb[i]], vv[i]);
+                if (save) keep[size_t(d) * kst + (size_t(ar) * CFO_TS + tt) * nd + i] = h;
+                if (dp < 0) continue;
+                const float2 c0 = cmulc(h, prev(i));
+                br += c0.x;
+                bi += c0.y;
+                const uint32_t j = i + static_cast<uint32_t>(sh);  // wraps below 0: out of range
+                if (sh != 0 && j < nd) {
+                    const float2 c1 = cmulc(h, prev(j));
+                    br += c1.x;
+                    bi += c1.y;
+                }
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                br += __shfl_xor(br, o);
+                bi += __shfl_xor(bi, o);
+            }
+            if (lane == 0) {
+                cr[p] = br;
+                ci[p] = bi;
+            }
+        }
+        __syncthreads();
+        if (cnt && dp >= 0) {  // no earlier op of the set, or no stream to measure: no update
+            double sr = 0.0, si = 0.0;
+            for (uint32_t p = 0; p < cnt; ++p) {
+                sr += cr[p];
+                si += ci[p];
+            }
+            const double theta = remainder(atan2(si, sr) + psi_d - psi[dp], 6.283185307179586476925);
+            const double nxt = run - A.gain * theta / static_cast<double>((l - lp) * A.sym_len);
+            a += static_cast<double>(l * A.sym_len) * (run - nxt);  // continuous at the first CP sample of l + 1
+            run = nxt;
+        }
+        __syncthreads();
+    }
+    for (uint32_t s = lf + threadIdx.x; s <= A.sym_last; s += CFO_THREADS) tab[s] = make_double2(a, run);
+    if (!A.is_pdc && threadIdx.x == 0) {
+        st->cfo_a = a;
+        st->cfo_run = run;
+        st->cfo_ops = d;
+    }
+}
+
+hipError_t launch_rx_cfo_track(const rx_cfo_args& a, uint32_t n, hipStream_t st) {
+    if (a.N_RX > 8 || a.n_dops > MAX_DOPS || a.sym_last >= a.n_sym_total || a.sym_first > a.sym_last || a.Nd > a.sym_len ||
+        !a.keep)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rx_cfo_track_kernel, dim3(n), dim3(CFO_THREADS), 0, st, a);
     return hipGetLastError();
 }
 

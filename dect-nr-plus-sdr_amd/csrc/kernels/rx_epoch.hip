@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
             if (t != w) __builtin_amdgcn_wave_barrier();  // the previous task's reads of R are done
             stage_span_row<10>(R, srow, in.fine_peak + sp.in0, sp.n_in, v0, F.S_in, lane);
             __builtin_amdgcn_wave_barrier();
-            rx_resample_ct<LR, MR, HLR>(F, in, S, sp, R, lane);
+            rx_resample_ct<LR, MR, HLR>(F, rx_cfo_of(F, in, S, F.STF_CP + 1024, pkt, l), sp, R, lane);
             const size_t yimg = experiment(XS_EP_SLOTY) ? blockIdx.x % (64u * A.n_epochs) : pkt;
             // plain pointer stores: with the stores through a row descriptor (as in rx_fft_wave_ct_kernel) this
             // kernel's build moved 2 of 4.4 million LLRs of a C4 chunk by one LSB (profiles/r09)

@@ -46,9 +46,17 @@ __device__ __forceinline__ rx_span_t rx_span(const rx_front_args& A, uint32_t l)
 #define DNRP_FE_IMAJ 0  // 1: the polyphase windows input-major from LDS (pp_const::run_imaj): rx_epoch 26.84 /
                         // 26.78 vs 26.62 / 26.69 ms (the kernel's VGPR peak is elsewhere), off
 #endif
-// R[i] = input in0 + i (staged), i < n_in  ->  R[j] = mixed output m0 + j, j < 1024
+// the mixer entry (phase a, increment) symbol l of a slot is mixed with: DECT-rate sample m gets the phase
+// a + (m - n_stf) inc. The packet's STF values (n_stf inc0, inc1), or with residual CFO tracking (A.cfo_sym,
+// a uniform test) the table entry rx_cfo_track_kernel wrote for the symbol
+__device__ __forceinline__ double2 rx_cfo_of(const rx_front_args& A, const rx_pkt_in& in, const rx_pkt_state& S,
+                                             uint32_t n_stf, uint32_t slot, uint32_t l) {
+    return A.cfo_sym ? A.cfo_sym[size_t(slot) * A.n_sym_total + l] : make_double2(static_cast<double>(n_stf) * in.inc0, S.inc1);
+}
+
+// R[i] = input in0 + i (staged), i < n_in  ->  R[j] = mixed output m0 + j, j < 1024; mix: rx_cfo_of
 template <int LR, int MR, int HLR>
-__device__ __forceinline__ void rx_resample_ct(const rx_front_args& A, const rx_pkt_in& in, const rx_pkt_state& S,
+__device__ __forceinline__ void rx_resample_ct(const rx_front_args& A, const double2 mix,
                                                const rx_span_t& sp, float2* R, uint32_t lane) {
     using PD = pp_direct<LR, MR, HLR>;
     static_assert(taps_rx_9_10::L == LR && taps_rx_9_10::M == MR && taps_rx_9_10::HL == HLR, "generated taps");
@@ -58,8 +66,8 @@ __device__ __forceinline__ void rx_resample_ct(const rx_front_args& A, const rx_
     // its outputs before the next round loads its windows
     static_assert(LR * (64 + 1) <= MR * 64, "round outputs stay below the next round's windows");
     const int n_stf = static_cast<int>(A.STF_CP + 1024);
-    const double phi_stf = static_cast<double>(n_stf) * in.inc0;  // mixer phase at the first data sample
-    const float2 step1 = phasor(S.inc1);
+    const double phi_stf = mix.x;  // mixer phase at the first data sample
+    const float2 step1 = phasor(mix.y);
 #pragma unroll
     for (int rd = 0; rd < BR; ++rd) {
         const int qr = static_cast<int>(lane) + 64 * rd;
@@ -75,7 +83,7 @@ __device__ __forceinline__ void rx_resample_ct(const rx_front_args& A, const rx_
         __builtin_amdgcn_wave_barrier();
         if (q < sp.qb1) {
             const int mb = static_cast<int>(A.m_star) + LR * q;
-            float2 r = phasor(phi_stf + static_cast<double>(mb - n_stf) * S.inc1);
+            float2 r = phasor(phi_stf + static_cast<double>(mb - n_stf) * mix.y);
 #pragma unroll
             for (int k = 0; k < LR; ++k) {
                 const uint32_t idx = static_cast<uint32_t>(mb + k - sp.m0);

@@ -238,7 +238,8 @@ EXPORTS = ["dnrp_ctx_create", "dnrp_ctx_destroy", "dnrp_add_network_id", "dnrp_g
            "dnrp_tx_window", "dnrp_ctx_set_sync_beta_search", "dnrp_ctx_get_sync_beta_search",
            "dnrp_ctx_set_sync_fine_all_antennas", "dnrp_ctx_get_sync_fine_all_antennas", "dnrp_rx_sync_fine_peaks",
            "dnrp_tx_last_form", "dnrp_tx_form_for", "dnrp_ctx_set_rx_sto_tracking", "dnrp_ctx_get_rx_sto_tracking",
-           "dnrp_rx_sto_track", "dnrp_ctx_set_rx_mimo_report", "dnrp_ctx_get_rx_mimo_report", "dnrp_rx_mimo_detail"]
+           "dnrp_rx_sto_track", "dnrp_ctx_set_rx_mimo_report", "dnrp_ctx_get_rx_mimo_report", "dnrp_rx_mimo_detail",
+           "dnrp_ctx_set_rx_cfo_tracking", "dnrp_ctx_get_rx_cfo_tracking", "dnrp_rx_cfo_track"]
 
 _lib = None
 
@@ -276,6 +277,9 @@ def lib():
         L.dnrp_ctx_get_sync_fine_all_antennas.argtypes = [P, C.POINTER(C.c_uint32)]
         L.dnrp_rx_sync_fine_peaks.argtypes = [P, C.c_uint32, P, P, P]
         L.dnrp_ctx_set_rx_sto_tracking.argtypes = [P, C.c_uint32, C.c_float]
+        L.dnrp_ctx_set_rx_cfo_tracking.argtypes = [P, C.c_uint32, C.c_float]
+        L.dnrp_ctx_get_rx_cfo_tracking.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+        L.dnrp_rx_cfo_track.argtypes = [P, C.c_uint32, P, P, C.c_uint32, C.POINTER(C.c_uint32), P]
         L.dnrp_ctx_get_rx_sto_tracking.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
         L.dnrp_rx_sto_track.argtypes = [P, C.c_uint32, P, C.c_uint32, C.POINTER(C.c_uint32), P]
         L.dnrp_ctx_set_rx_mimo_report.argtypes = [P, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -602,6 +606,34 @@ class Phy:
              "dnrp_rx_mimo_detail")
         self.sync(stream)
         return out
+
+    def set_rx_cfo_tracking(self, on, gain=1.0):
+        """dnrp_ctx_set_rx_cfo_tracking: every later rx_pcc_batch (and its rx_pdc_batch) takes, after each DRS
+        symbol that has an earlier one of the same transmit streams, gain times the rotation between the two per
+        sample off the mixer increment of the later symbols (the intent of the reference's build option
+        RX_SYNCED_PARAM_CFO_RESIDUAL_BASED_ON_DRS); off (the default) mixes every symbol with the STF's increment."""
+        _chk(lib().dnrp_ctx_set_rx_cfo_tracking(self._ctx, int(on), float(gain)), "dnrp_ctx_set_rx_cfo_tracking")
+
+    def rx_cfo_tracking(self):
+        """dnrp_ctx_get_rx_cfo_tracking: (on, gain)."""
+        on, gain = C.c_uint32(), C.c_float()
+        _chk(lib().dnrp_ctx_get_rx_cfo_tracking(self._ctx, C.byref(on), C.byref(gain)), "dnrp_ctx_get_rx_cfo_tracking")
+        return bool(on.value), gain.value
+
+    def rx_cfo_track(self, n_slots, stream=None):
+        """dnrp_rx_cfo_track: float64 [n_slots, n_sym, 2], the mixer entry (phase a, increment) each OFDM symbol of
+        the first n_slots PCC-batch slots was mixed with by the latest rx_pcc_batch / rx_pdc_batch, which ran with
+        set_rx_cfo_tracking(1): DECT-rate sample m of symbol l got the phase a + (m - n_stf) inc. NaN where a
+        symbol was not processed. Synchronises the stream before it returns."""
+        n_sym = C.c_uint32()
+        _chk(lib().dnrp_rx_cfo_track(self._ctx, int(n_slots), None, None, 0, C.byref(n_sym), _stream_ptr(stream)),
+             "dnrp_rx_cfo_track")
+        inc = np.full((int(n_slots), n_sym.value), np.nan, np.float64)
+        phase = np.full((int(n_slots), n_sym.value), np.nan, np.float64)
+        _chk(lib().dnrp_rx_cfo_track(self._ctx, int(n_slots), C.c_void_p(inc.ctypes.data), C.c_void_p(phase.ctypes.data),
+                                     n_sym.value, C.byref(n_sym), _stream_ptr(stream)), "dnrp_rx_cfo_track")
+        self.sync(stream)
+        return np.stack([phase, inc], axis=2)
 
     def add_network_id(self, nid):
         _chk(lib().dnrp_add_network_id(self._ctx, nid), "dnrp_add_network_id")

@@ -417,6 +417,46 @@ int dnrp_ctx_get_rx_sto_tracking(const dnrp_ctx* ctx, uint32_t* on, float* gain)
 int dnrp_rx_sto_track(dnrp_ctx* ctx, uint32_t n_slots, double* inc, uint32_t n_sym_cap, uint32_t* n_sym, void* stream);
 
 /*
+ * Residual CFO tracking from the DRS symbols <- the intent of the build option
+ * RX_SYNCED_PARAM_CFO_RESIDUAL_BASED_ON_DRS (rx_synced_param.hpp:162-181: "two OFDM symbols with DRS cells are
+ * compared, their spacing in time domain is N_step"; rx_synced.cpp:843-852), which the reference comments out
+ * as not functional: its estimator_cfo.cpp:65-74 multiplies neighbouring cells of one symbol, which measures a
+ * timing slope. The sister of dnrp_ctx_set_rx_sto_tracking: carrier and sampling clock share one oscillator.
+ *   on  0 (default): exactly the receiver without the option: every data-field symbol of a packet is mixed
+ *       with the increment the STF refined, the same launches, byte-identical LLRs and reports.
+ *       1: after every DRS symbol l that has an earlier DRS symbol l' of the same transmit streams, the rotation
+ *       between the two -- the angle of C = sum h_l[i] conj(h_l'[i]) + h_l[i] conj(h_l'[i -+ 1]) over the
+ *       zero-forced pilots i, the streams TS_first..min(TS_last, 7) and the RX antennas, the two cells of l'
+ *       being those on either side of cell i, so that a timing offset cancels to first order -- less what the
+ *       table has already removed, divided by (l - l') (CP + N_b_DFT_os) samples and times `gain`, is taken off
+ *       the mixer increment of every later symbol; the mixer phase stays continuous at the first CP sample of
+ *       symbol l + 1 (mixer.cpp adjust_phase_increment). A DRS symbol itself is mixed with the values from before
+ *       its own update. The PDC phase continues from the PCC phase's state. The fused receiver
+ *       (DNRP_RX_FUSED) and the grouped Y path (DNRP_RX_GROUP) are not taken while it is on. It may be on
+ *       together with STO tracking: both measure the same rows, front-ended with the STF values alone.
+ *   gain  scales each residual: 0 runs the whole mechanism with every symbol's entry equal to the STF values
+ *       (LLRs byte-identical to off).
+ * Read once per dnrp_rx_pcc_batch; that call's dnrp_rx_pdc_batch takes the same values. With it on, a
+ * dnrp_rx_pdc_batch request for spatial multiplexing returns DNRP_EUNSUPPORTED before anything is launched.
+ * DNRP_EINVAL for a NULL context, on > 1, a non-finite gain or a gain outside [0, 1]; a refused call changes
+ * nothing. The getter's outputs may be NULL.
+ *
+ * dnrp_rx_cfo_track: stream-ordered copy of the mixer entry every OFDM symbol was mixed with by the latest
+ * dnrp_rx_pcc_batch / dnrp_rx_pdc_batch: inc and phase are host arrays [n_slots][*n_sym] (either may be NULL),
+ * slot = index in the PCC batch, *n_sym = symbols the PCC call's windows hold + 1. The mixer phase of DECT-rate
+ * sample m of symbol l (counted from the packet's first sample, CP included) is
+ * phase[l] + (m - n_stf) inc[l], n_stf = STF_CP + N_b_DFT_os samples; without an update the entry is
+ * (n_stf inc0, inc1), the sync report's increment and the STF's. Symbols that were not processed hold NaN.
+ * inc and phase NULL: only *n_sym is written (size query). Valid once `stream` has been synchronised.
+ * DNRP_EINVAL while the latest PCC call ran with tracking off or there was none, for n_slots = 0 or beyond
+ * that call's n, or n_sym_cap < *n_sym.
+ */
+int dnrp_ctx_set_rx_cfo_tracking(dnrp_ctx* ctx, uint32_t on, float gain);
+int dnrp_ctx_get_rx_cfo_tracking(const dnrp_ctx* ctx, uint32_t* on, float* gain);
+int dnrp_rx_cfo_track(dnrp_ctx* ctx, uint32_t n_slots, double* inc, double* phase, uint32_t n_sym_cap, uint32_t* n_sym,
+                      void* stream);
+
+/*
  * MIMO report options <- the build options RX_SYNCED_PARAM_MODE_3_7_METRIC and
  * RX_SYNCED_PARAM_MIMO_USE_ALL_W_MATRICES_OR_ONLY_NON_ZERO (lib/include/dectnrp/phy/rx/rx_synced/
  * rx_synced_param.hpp:273-286; estimator_mimo.cpp:162-271), a read-back of the report's inputs and scores, and
