@@ -27,76 +27,84 @@ struct rx_phase {
     bool sm;  // spatial multiplexing: the MMSE cells kernel
 };
 
+// the phase's DRS ops as the SNR chain, the trackers and the cells kernels see them
+dev::rx_drs_view drs_view(dnrp_ctx* ctx, const rx_phase& p) {
+    dev::rx_drs_view v{};
+    v.N_RX = ctx->cfg.N_TX_max;
+    v.Nf_pad = ctx->rx_Nf_pad;
+    v.n_sym_total = ctx->rx_nsym_cap + 1;
+    v.n_drs = p.t->N_occ / 4;
+    v.n_dops = p.plan->n_dops;
+    v.is_pdc = p.pdc;
+    v.dl = p.plan->dl.as<uint32_t>();
+    v.dmeta = p.plan->dmeta.as<uint32_t>();
+    v.drs_k = p.t->drs_k.as<uint32_t>();
+    v.drs_v = p.t->drs_v.as<float>();
+    v.Y = ctx->Y.as<float2>();
+    v.st = ctx->rx_st.as<dev::rx_pkt_state>();
+    v.sel = p.sel;
+    return v;
+}
+
 // the cells kernels' arguments of one phase (rx_cells_kernel, rx_epoch_kernel). lut_d and nv_d are
 // sized by dnrp_rx_pcc_batch, so their addresses hold whenever a block is built
 dev::rx_cells_args cells_args(dnrp_ctx* ctx, const rx_phase& p) {
     const rx1_tables* t = p.t;
+    const dev::rx_drs_view v = drs_view(ctx, p);
     dev::rx_cells_args c{};
     c.N_occ = t->N_occ;
-    c.N_RX = ctx->cfg.N_TX_max;
+    c.N_RX = v.N_RX;
     c.NT = t->N_eff_TX;
-    c.Nf_pad = ctx->rx_Nf_pad;
-    c.n_sym_total = ctx->rx_nsym_cap + 1;
-    c.n_drs = t->N_occ / 4;
-    c.n_dops = p.plan->n_dops;
+    c.Nf_pad = v.Nf_pad;
+    c.n_sym_total = v.n_sym_total;
+    c.n_drs = v.n_drs;
+    c.n_dops = v.n_dops;
     c.n_epochs = p.plan->n_epochs;
     c.n_pkt = p.n;
     c.N_bps = p.N_bps;
     c.wcap[0] = t->wcap[0];
     c.wcap[1] = t->wcap[1];
     fill_pairs(t->N_eff_TX, c.pair, c.mod);
-    c.is_pdc = p.pdc;
+    c.is_pdc = v.is_pdc;
     c.sm = p.sm ? 1u : 0u;
     c.nv_d = ctx->nv_d.as<float>();
     c.epochs = p.plan->epochs.as<dev::rx_epoch>();
     c.segs = p.plan->segs.as<dev::rx_seg>();
-    c.dl = p.plan->dl.as<uint32_t>();
-    c.dmeta = p.plan->dmeta.as<uint32_t>();
-    c.drs_k = t->drs_k.as<uint32_t>();
-    c.drs_v = t->drs_v.as<float>();
+    c.dl = v.dl;
+    c.dmeta = v.dmeta;
+    c.drs_k = v.drs_k;
+    c.drs_v = v.drs_v;
     c.kk = p.kk;
     c.cell_sym = p.cell_sym;
     c.luts = t->luts.as<dev::rx_lut>();
-    c.Y = ctx->Y.as<float2>();
+    c.Y = v.Y;
     c.lut_d = ctx->lut_d.as<uint8_t>();
     c.pcc_seq = ctx->pcc_seq.as<uint8_t>();
     c.pdc_seq = static_cast<const uint8_t* const*>(ctx->pdc_seq_ptrs.p);
     c.llr = p.llr;
     c.llr_stride = p.llr_stride;
-    c.sel = p.sel;
+    c.sel = v.sel;
     return c;
 }
 
-// back-end launches of one phase: the SNR chain, then the cells kernel on c (rx_back.hip); c null: the
-// SNR chain only (launch_snr_chain)
+// back-end launches of one phase: the SNR chain (rx_drs.hip), then the cells kernel on c (rx_cells.hip); c
+// null: the SNR chain only (launch_snr_chain)
 int launch_back(dnrp_ctx* ctx, const rx_phase& p, const dev::rx_cells_args* c, hipStream_t st) {
     rx1_tables* t = p.t;
     const rx_plan_dev& plan = *p.plan;
     const char* name = p.pdc ? "rx_pdc" : "rx_pcc";
     if (plan.n_dops > dev::RX_MAX_DOPS || (c && !plan.cells_ok)) return DNRP_EUNSUPPORTED;
-    if (c) {  // the cells kernels' LDS staging (rx_back.hip): a geometry beyond one CU is unsupported
+    if (c) {  // the cells kernels' LDS staging (rx_cells.hip): a geometry beyond one CU is unsupported
         const uint32_t R = ctx->cfg.N_TX_max, T = t->N_eff_TX;
-        if (dev::cell_lds_bytes(R, T, t->N_occ / 4, t->wcap[0], t->wcap[1]) > 160 * 1024) return DNRP_EUNSUPPORTED;
+        if (dev::cell_lds_bytes(R, T, t->N_occ / 4, t->wcap[0], t->wcap[1]) > dev::LDS_BYTES) return DNRP_EUNSUPPORTED;
         // the MMSE cells kernel's instantiations
-        if (p.sm && !((R == 2 || R == 4 || R == 8) && (T == 2 || T == 4) && T <= R)) return DNRP_EUNSUPPORTED;
+        if (p.sm && !dev::rx_cells_supported(R, T, true)) return DNRP_EUNSUPPORTED;
     }
     dev::rx_snr_args s{};
-    s.N_RX = ctx->cfg.N_TX_max;
-    s.Nf_pad = ctx->rx_Nf_pad;
-    s.n_sym_total = ctx->rx_nsym_cap + 1;
-    s.n_drs = t->N_occ / 4;
-    s.n_dops = plan.n_dops;
-    s.is_pdc = p.pdc;
-    s.dl = plan.dl.as<uint32_t>();
-    s.dmeta = plan.dmeta.as<uint32_t>();
-    s.drs_k = t->drs_k.as<uint32_t>();
-    s.drs_v = t->drs_v.as<float>();
+    s.V = drs_view(ctx, p);
     for (int i = 0; i < 3; ++i) s.prof_snr[i] = geo::lut_profile_snr_db(i);
-    s.Y = ctx->Y.as<float2>();
-    s.st = ctx->rx_st.as<dev::rx_pkt_state>();
     s.lut_d = ctx->lut_d.as<uint8_t>();
     s.nv_d = ctx->nv_d.as<float>();
-    s.sel = p.sel;
     s.snr_part = snr_from_front(ctx, t) ? ctx->snr_part.as<double2>() : nullptr;
     ctx->tic(name, st);
     if (dev::launch_rx_snr(s, p.n, st) != hipSuccess) return DNRP_EDEVICE;
@@ -197,11 +205,11 @@ pdc_path choose_pdc_path(const switches& sw, const rx1_tables* t, const rx2_tabl
     // both fused forms: the compile-time-tap wave front end and an instantiated (N_RX, N_eff_TX) pair
     const bool wave = fa.stream && dev::rx_fft_wave_path(fa);
     if (!sto_track && sw.rx_fused && t2->fused_ok && fa.zd && wave && dev::rx_fused_supported(fa.N_RX, t->N_eff_TX) &&
-        dev::rx_fused_lds(fa.N_RX) <= 160 * 1024)
+        dev::rx_fused_lds(fa.N_RX) <= dev::LDS_BYTES)
         return pdc_path::fused;
     if ((sw.rx_epoch >= 2 || (sw.rx_epoch == 1 && fa.N_RX >= 4)) && t2->ep_ok && !t2->sm && wave &&
         t2->bplan.cells_ok && t2->bplan.n_epochs && dev::rx_epoch_supported(fa.N_RX, t->N_eff_TX) &&
-        dev::rx_epoch_lds(ca) <= 160 * 1024)
+        dev::rx_epoch_lds(ca) <= dev::LDS_BYTES)
         return pdc_path::epoch;
     if (!sto_track && sw.rx_group && ng > sw.rx_group && t2->q.N_DF_symb > t->pcc_max) return pdc_path::grouped_y;
     return pdc_path::plain_y;
@@ -228,84 +236,58 @@ int launch_fft_list(dnrp_ctx* ctx, dev::rx_front_args fa, const uint16_t* syms, 
     return DNRP_OK;
 }
 
-// residual STO tracking of one phase (rx_sto_track_kernel): the phase's DRS rows are in Y, derotated with
-// the STF increment; fills the table entries of the symbols [sym_first, sym_last]
-int launch_sto_track(dnrp_ctx* ctx, const rx_phase& p, uint32_t sym_first, uint32_t sym_last, hipStream_t st) {
-    const rx1_tables* t = p.t;
-    dev::rx_sto_args a{};
-    a.N_RX = ctx->cfg.N_TX_max;
-    a.Nf_pad = ctx->rx_Nf_pad;
-    a.n_sym_total = ctx->rx_nsym_cap + 1;
-    a.n_drs = t->N_occ / 4;
-    a.n_dops = p.plan->n_dops;
-    a.N_occ = t->N_occ;
-    a.is_pdc = p.pdc;
-    a.sym_first = sym_first;
-    a.sym_last = sym_last;
-    a.gain = ctx->rx_sto_gain;
-    a.dl = p.plan->dl.as<uint32_t>();
-    a.dmeta = p.plan->dmeta.as<uint32_t>();
-    a.drs_k = t->drs_k.as<uint32_t>();
-    a.drs_v = t->drs_v.as<float>();
-    a.Y = ctx->Y.as<float2>();
-    a.st = ctx->rx_st.as<dev::rx_pkt_state>();
-    a.sel = p.sel;
-    a.tab = ctx->sto_sym.as<double>();
-    ctx->tic("rx_sto_track", st);
-    if (dev::launch_rx_sto_track(a, p.n, st) != hipSuccess) return DNRP_EDEVICE;
-    ctx->toc("rx_sto_track", st);
-    return DNRP_OK;
-}
-
-// residual CFO tracking of one phase (rx_cfo_track_kernel) on the same rows, mixed with the STF values; fills
-// the mixer table entries of the symbols [sym_first, sym_last]
-int launch_cfo_track(dnrp_ctx* ctx, const rx_phase& p, uint32_t sym_first, uint32_t sym_last, hipStream_t st) {
-    const rx1_tables* t = p.t;
-    if (t->bplan.n_dops > dev::RX_CFO_KEEP) return DNRP_EUNSUPPORTED;  // the PCC phase's pilots kept for the PDC phase
-    dev::rx_cfo_args a{};
-    a.N_RX = ctx->cfg.N_TX_max;
-    a.Nf_pad = ctx->rx_Nf_pad;
-    a.n_sym_total = ctx->rx_nsym_cap + 1;
-    a.n_drs = t->N_occ / 4;
-    a.n_dops = p.plan->n_dops;
-    a.is_pdc = p.pdc;
-    a.sym_first = sym_first;
-    a.sym_last = sym_last;
-    a.n_stf = t->STF_CP + t->Nd;
-    a.sym_len = t->CP + t->Nd;
-    a.Nd = t->Nd;
-    a.gain = ctx->rx_cfo_gain;
-    a.dl = p.plan->dl.as<uint32_t>();
-    a.dmeta = p.plan->dmeta.as<uint32_t>();
-    a.drs_k = t->drs_k.as<uint32_t>();
-    a.drs_v = t->drs_v.as<float>();
-    a.Y = ctx->Y.as<float2>();
-    a.pin = ctx->rx_in.as<dev::rx_pkt_in>();
-    a.st = ctx->rx_st.as<dev::rx_pkt_state>();
-    a.sel = p.sel;
-    a.tab = ctx->cfo_sym.as<double2>();
-    a.keep = ctx->cfo_keep.as<float2>();
-    ctx->tic("rx_cfo_track", st);
-    if (dev::launch_rx_cfo_track(a, p.n, st) != hipSuccess) return DNRP_EDEVICE;
-    ctx->toc("rx_cfo_track", st);
-    return DNRP_OK;
-}
-
-// the trackers that are on, over one phase's symbols, on the Y rows a DRS pass with the STF values left (one
-// pass for both: each measures the same rows); fa then carries their tables for the phase's launches
+// the trackers that are on, over one phase's symbols [sym_first, sym_last], on the Y rows a DRS pass with the STF
+// values left (one pass for both: each measures the same rows; rx_sto_track_kernel, then rx_cfo_track_kernel);
+// fa then carries their tables for the phase's launches
 int launch_track(dnrp_ctx* ctx, const rx_phase& p, uint32_t sym_first, uint32_t sym_last, dev::rx_front_args& fa,
                  hipStream_t st) {
-    int err = DNRP_OK;
-    if (ctx->rx_sto_on) err = launch_sto_track(ctx, p, sym_first, sym_last, st);
-    if (err == DNRP_OK && ctx->rx_cfo_on) err = launch_cfo_track(ctx, p, sym_first, sym_last, st);
-    if (ctx->rx_sto_on) fa.sto_sym = ctx->sto_sym.as<double>();
-    if (ctx->rx_cfo_on) fa.cfo_sym = ctx->cfo_sym.as<double2>();
-    return err;
+    const rx1_tables* t = p.t;
+    auto common = [&](dev::rx_track_args& a, double gain) {
+        a.V = drs_view(ctx, p);
+        a.sym_first = sym_first;
+        a.sym_last = sym_last;
+        a.gain = gain;
+    };
+    if (ctx->rx_sto_on) {
+        dev::rx_sto_args a{};
+        common(a, ctx->rx_sto_gain);
+        a.N_occ = t->N_occ;
+        a.tab = ctx->sto_sym.as<double>();
+        ctx->tic("rx_sto_track", st);
+        if (dev::launch_rx_sto_track(a, p.n, st) != hipSuccess) return DNRP_EDEVICE;
+        ctx->toc("rx_sto_track", st);
+        fa.sto_sym = a.tab;
+    }
+    if (ctx->rx_cfo_on) {
+        if (t->bplan.n_dops > dev::RX_CFO_KEEP) return DNRP_EUNSUPPORTED;  // the PCC phase's pilots kept for the PDC phase
+        dev::rx_cfo_args a{};
+        common(a, ctx->rx_cfo_gain);
+        a.n_stf = t->STF_CP + t->Nd;
+        a.sym_len = t->CP + t->Nd;
+        a.Nd = t->Nd;
+        a.pin = ctx->rx_in.as<dev::rx_pkt_in>();
+        a.tab = ctx->cfo_sym.as<double2>();
+        a.keep = ctx->cfo_keep.as<float2>();
+        ctx->tic("rx_cfo_track", st);
+        if (dev::launch_rx_cfo_track(a, p.n, st) != hipSuccess) return DNRP_EDEVICE;
+        ctx->toc("rx_cfo_track", st);
+        fa.cfo_sym = a.tab;
+    }
+    return DNRP_OK;
 }
 
-// the PDC phase's part of residual STO / CFO tracking
-int pdc_track(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_front_args& fa, hipStream_t st) {
-    return launch_track(ctx, p, p.t->pcc_max + 1, t2->q.N_DF_symb, fa, st);
+// A phase's front-end launches `pass(fa)` under residual STO / CFO tracking: first `pre(fa)`, launches that leave
+// the phase's DRS rows in Y with the STF values, then the trackers on those rows, then `pass` with their tables
+// in fa. Without tracking: `pass` alone.
+template <class Pre, class Pass>
+int tracked_pass(dnrp_ctx* ctx, const rx_phase& p, uint32_t sym_first, uint32_t sym_last, dev::rx_front_args& fa,
+                 hipStream_t st, Pre&& pre, Pass&& pass) {
+    if (rx_tracking(ctx)) {
+        int err = pre(fa);
+        if (err == DNRP_OK) err = launch_track(ctx, p, sym_first, sym_last, fa, st);
+        if (err != DNRP_OK) return err;
+    }
+    return pass(fa);
 }
 
 // the phase's DRS symbols first (pilots, SNR sums; their bins to Y only where they carry PDC cells),
@@ -343,11 +325,10 @@ int pdc_fused(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_fr
 // with their tables, which the epoch kernel's front end takes too
 int pdc_epoch(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_front_args fa,
               const dev::rx_cells_args& ca, hipStream_t st) {
-    int err = launch_fft_list(ctx, fa, t2->ep_drs.as<uint16_t>(), t2->n_ep_drs, p.n, st);
-    if (err == DNRP_OK && rx_tracking(ctx)) {
-        err = pdc_track(ctx, p, t2, fa, st);
-        if (err == DNRP_OK) err = launch_fft_list(ctx, fa, t2->ep_drs.as<uint16_t>(), t2->n_ep_drs, p.n, st);
-    }
+    auto drs_pass = [&](const dev::rx_front_args& f) {
+        return launch_fft_list(ctx, f, t2->ep_drs.as<uint16_t>(), t2->n_ep_drs, p.n, st);
+    };
+    int err = tracked_pass(ctx, p, p.t->pcc_max + 1, t2->q.N_DF_symb, fa, st, drs_pass, drs_pass);
     if (err == DNRP_OK) err = launch_snr_chain(ctx, p, st);
     if (err != DNRP_OK) return err;
     dev::rx_epoch_args x{};
@@ -403,16 +384,20 @@ int pdc_grouped_y(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::r
 int pdc_plain_y(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, dev::rx_front_args fa,
                 const dev::rx_cells_args& ca, hipStream_t st) {
     if (t2->q.N_DF_symb > p.t->pcc_max) {
-        if (rx_tracking(ctx)) {  // the phase's DRS symbols (the plan's ops behind the PCC phase's) first
-            const uint32_t d0 = p.t->bplan.n_dops, nd = p.plan->n_dops - d0;
-            int err = launch_fft_list(ctx, fa, p.plan->dl16.as<uint16_t>() + d0, nd, p.n, st, p.plan->dl_h.data() + d0);
-            if (err == DNRP_OK) err = pdc_track(ctx, p, t2, fa, st);
-            if (err != DNRP_OK) return err;
-        }
         fa.sym_count = t2->q.N_DF_symb - p.t->pcc_max;
-        ctx->tic("rx_fft_pdc", st);
-        if (dev::launch_rx_fft(fa, p.n, st) != hipSuccess) return DNRP_EDEVICE;
-        ctx->toc("rx_fft_pdc", st);
+        const int err = tracked_pass(
+            ctx, p, p.t->pcc_max + 1, t2->q.N_DF_symb, fa, st,
+            [&](const dev::rx_front_args& f) {  // the phase's DRS symbols: the plan's ops behind the PCC phase's
+                const uint32_t d0 = p.t->bplan.n_dops, nd = p.plan->n_dops - d0;
+                return launch_fft_list(ctx, f, p.plan->dl16.as<uint16_t>() + d0, nd, p.n, st, p.plan->dl_h.data() + d0);
+            },
+            [&](const dev::rx_front_args& f) {
+                ctx->tic("rx_fft_pdc", st);
+                if (dev::launch_rx_fft(f, p.n, st) != hipSuccess) return DNRP_EDEVICE;
+                ctx->toc("rx_fft_pdc", st);
+                return DNRP_OK;
+            });
+        if (err != DNRP_OK) return err;
     }
     return launch_back(ctx, p, &ca, st);
 }
@@ -529,6 +514,35 @@ int pdc_reports(dnrp_ctx* ctx, uint32_t m, const dnrp_pdc_req* req, dnrp_pdc_rep
         rep[r].tm_3_7_beamforming_reciprocal_idx = mo[3 * r + 2];
     }
     return DNRP_OK;
+}
+
+}  // namespace
+
+namespace {
+
+// the two residual tracking settings (dnrp_ctx_set_rx_sto_tracking, dnrp_ctx_set_rx_cfo_tracking) and their tables
+int set_tracking(uint32_t& to_on, float& to_gain, uint32_t on, float gain) {
+    if (on > 1 || !std::isfinite(gain) || gain < 0.0f || gain > 1.0f) return DNRP_EINVAL;
+    to_on = on;
+    to_gain = gain;
+    return DNRP_OK;
+}
+
+int get_tracking(uint32_t from_on, float from_gain, uint32_t* on, float* gain) {
+    if (on) *on = from_on;
+    if (gain) *gain = from_gain;
+    return DNRP_OK;
+}
+
+// the common part of the table read-backs: *n_sym, and the table rows to copy (the device selected), 0
+// (DNRP_OK) for a size query, or an error
+int track_rows(dnrp_ctx* ctx, bool on, bool copy, uint32_t n_slots, uint32_t n_sym_cap, uint32_t* n_sym) {
+    if (!ctx || !n_sym || !ctx->rx_valid || !on) return DNRP_EINVAL;
+    *n_sym = ctx->rx_nsym_cap + 1;
+    if (!copy) return DNRP_OK;
+    if (n_slots == 0 || n_slots > ctx->rx_n || n_sym_cap < *n_sym) return DNRP_EINVAL;
+    (void)hipSetDevice(ctx->cfg.device);
+    return static_cast<int>(n_slots * *n_sym);
 }
 
 }  // namespace
@@ -658,14 +672,14 @@ int dnrp_rx_pcc_batch(dnrp_ctx* ctx, uint32_t n, const dnrp_sync_report* sr, con
         const rx_phase p{t, &t->bplan, ng, gsel, false, 2, t->pcc_k.as<uint32_t>(), t->pcc_sym.as<uint16_t>(), pcc_llr, 196, false};
         // residual STO / CFO tracking: the phase's few symbols with the STF values, the tables from their DRS
         // rows, then the same launch again with the tables
-        for (int pass = rx_tracking(ctx) ? 0 : 1; pass < 2; ++pass) {
+        auto fft_pcc = [&](const dev::rx_front_args& f) {
             ctx->tic("rx_fft_pcc", st);
-            if (dev::launch_rx_fft(fa, ng, st) != hipSuccess) return DNRP_EDEVICE;
+            if (dev::launch_rx_fft(f, ng, st) != hipSuccess) return DNRP_EDEVICE;
             ctx->toc("rx_fft_pcc", st);
-            if (pass) break;
-            err = launch_track(ctx, p, 0, t->pcc_max, fa, st);
-            if (err != DNRP_OK) return err;
-        }
+            return DNRP_OK;
+        };
+        err = tracked_pass(ctx, p, 0, t->pcc_max, fa, st, fft_pcc, fft_pcc);
+        if (err != DNRP_OK) return err;
         const auto ca = cells_args(ctx, p);
         err = launch_back(ctx, p, &ca, st);
         if (err != DNRP_OK) return err;
@@ -798,53 +812,34 @@ int dnrp_rx_mimo_detail(dnrp_ctx* ctx, uint32_t m, dnrp_mimo_detail* out, void* 
 }
 
 int dnrp_ctx_set_rx_sto_tracking(dnrp_ctx* ctx, uint32_t on, float gain) {
-    if (!ctx || on > 1 || !std::isfinite(gain) || gain < 0.0f || gain > 1.0f) return DNRP_EINVAL;
-    ctx->sto_track_on = on;
-    ctx->sto_track_gain = gain;
-    return DNRP_OK;
+    return ctx ? set_tracking(ctx->sto_track_on, ctx->sto_track_gain, on, gain) : DNRP_EINVAL;
 }
 
 int dnrp_ctx_get_rx_sto_tracking(const dnrp_ctx* ctx, uint32_t* on, float* gain) {
-    if (!ctx) return DNRP_EINVAL;
-    if (on) *on = ctx->sto_track_on;
-    if (gain) *gain = ctx->sto_track_gain;
-    return DNRP_OK;
+    return ctx ? get_tracking(ctx->sto_track_on, ctx->sto_track_gain, on, gain) : DNRP_EINVAL;
 }
 
 int dnrp_rx_sto_track(dnrp_ctx* ctx, uint32_t n_slots, double* inc, uint32_t n_sym_cap, uint32_t* n_sym, void* stream) {
-    if (!ctx || !n_sym || !ctx->rx_valid || !ctx->rx_sto_on) return DNRP_EINVAL;
-    *n_sym = ctx->rx_nsym_cap + 1;
-    if (!inc) return DNRP_OK;  // size query
-    if (n_slots == 0 || n_slots > ctx->rx_n || n_sym_cap < *n_sym) return DNRP_EINVAL;
-    (void)hipSetDevice(ctx->cfg.device);
-    HIPCHK(hipMemcpyAsync(inc, ctx->sto_sym.p, size_t(n_slots) * *n_sym * sizeof(double), hipMemcpyDeviceToHost,
+    const int rows = track_rows(ctx, ctx && ctx->rx_sto_on, inc != nullptr, n_slots, n_sym_cap, n_sym);
+    if (rows <= 0) return rows;
+    HIPCHK(hipMemcpyAsync(inc, ctx->sto_sym.p, size_t(rows) * sizeof(double), hipMemcpyDeviceToHost,
                           static_cast<hipStream_t>(stream)));
     return DNRP_OK;
 }
 
 int dnrp_ctx_set_rx_cfo_tracking(dnrp_ctx* ctx, uint32_t on, float gain) {
-    if (!ctx || on > 1 || !std::isfinite(gain) || gain < 0.0f || gain > 1.0f) return DNRP_EINVAL;
-    ctx->cfo_track_on = on;
-    ctx->cfo_track_gain = gain;
-    return DNRP_OK;
+    return ctx ? set_tracking(ctx->cfo_track_on, ctx->cfo_track_gain, on, gain) : DNRP_EINVAL;
 }
 
 int dnrp_ctx_get_rx_cfo_tracking(const dnrp_ctx* ctx, uint32_t* on, float* gain) {
-    if (!ctx) return DNRP_EINVAL;
-    if (on) *on = ctx->cfo_track_on;
-    if (gain) *gain = ctx->cfo_track_gain;
-    return DNRP_OK;
+    return ctx ? get_tracking(ctx->cfo_track_on, ctx->cfo_track_gain, on, gain) : DNRP_EINVAL;
 }
 
 int dnrp_rx_cfo_track(dnrp_ctx* ctx, uint32_t n_slots, double* inc, double* phase, uint32_t n_sym_cap, uint32_t* n_sym,
                       void* stream) {
-    if (!ctx || !n_sym || !ctx->rx_valid || !ctx->rx_cfo_on) return DNRP_EINVAL;
-    *n_sym = ctx->rx_nsym_cap + 1;
-    if (!inc && !phase) return DNRP_OK;  // size query
-    if (n_slots == 0 || n_slots > ctx->rx_n || n_sym_cap < *n_sym) return DNRP_EINVAL;
-    (void)hipSetDevice(ctx->cfg.device);
+    const int rows = track_rows(ctx, ctx && ctx->rx_cfo_on, inc || phase, n_slots, n_sym_cap, n_sym);
+    if (rows <= 0) return rows;
     // the device table holds (phase, increment) pairs: one strided copy per output array
-    const size_t rows = size_t(n_slots) * *n_sym;
     const auto* src = static_cast<const char*>(ctx->cfo_sym.p);
     if (phase)
         HIPCHK(hipMemcpy2DAsync(phase, sizeof(double), src, sizeof(double2), sizeof(double), rows, hipMemcpyDeviceToHost,

@@ -338,7 +338,7 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
     }
     a.fine_all = ctx->sync_fine_all;
     a.det_stage = dev::sync_detect_stage(a);
-    if (dev::sync_detect_lds(a) > 160 * 1024 || !dev::sync_fine_ok(a))
+    if (dev::sync_detect_lds(a) > dev::LDS_BYTES || !dev::sync_fine_ok(a))
         return DNRP_EUNSUPPORTED;
     const size_t nsa = size_t(n) * a.n_ant * a.n_steps;
     if (!ctx->sy_P.ensure(nsa * sizeof(float)) || !ctx->sy_C.ensure(nsa * sizeof(float2)) ||

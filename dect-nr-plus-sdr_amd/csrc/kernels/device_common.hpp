@@ -832,6 +832,15 @@ __device__ __forceinline__ void wave_fft1024_rt(float2 (&v)[16], float2* xb, con
     wave_fft1024_rt<SIGN>(v, xb, wfft_tw<SIGN>(tw, 4 * (lane & 15u)), wfft_tw<SIGN>(tw, lane), lane);
 }
 
+// wave-wide sums of two doubles (.x of a, .y of b), valid in all lanes
+__device__ __forceinline__ double2 wave_sum2(double a, double b) {
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o);
+        b += __shfl_xor(b, o);
+    }
+    return make_double2(a, b);
+}
+
 // block-wide sum of a double, result valid in all threads (blockDim.x multiple of 64, <= 1024)
 // three block sums with one set of barriers (each value summed exactly as block_sum sums it);
 // red holds >= 3 * waves doubles

@@ -5,10 +5,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "device_common.hpp"
 #include "../params.hpp"
 
 namespace dnrp::dev {
+
+constexpr size_t LDS_BYTES = 160 * 1024;  // LDS of one CDNA4 compute unit, all of it available to one workgroup
 
 // TX cell codes: type in bits 29-31; PCC/PDC: cell index j in bits 0-19 and the transmit
 // diversity TS pair A | B << 4 of cell j (pair table entry (j >> 1) % mod) in bits 20-27
@@ -171,7 +175,7 @@ struct rx_front_args {
     // cell i at occupied index 4 i + (t + 2 p) % 4 (DC skipped), value -+1 from drs_neg bit
     // (4 i + t % 4) % 56, negated for t >= 4 (drs.cpp:196-254; host-checked against drs_k / drs_v)
     double2* snr_part;
-    const uint32_t* dl;        // the phase plan's DRS ops (rx_snr_args)
+    const uint32_t* dl;        // the phase plan's DRS ops (rx_drs_view)
     const uint32_t* dmeta;
     uint64_t drs_neg;          // bit j: y_b_1[j] = -1 (drs.hpp)
     const uint16_t* sym_op;    // [n_sym_op]: first DRS op of symbol l, 0xFFFF: none
@@ -216,6 +220,22 @@ __device__ __forceinline__ uint32_t rx_slot_of(const uint32_t* sel, uint32_t i) 
 __device__ __forceinline__ uint32_t rx_row_of(const uint32_t* sel, uint32_t i) { return sel[2 * i + 1]; }
 constexpr uint32_t RX_MAX_DOPS = 64;  // DRS ops per phase; lut_d holds RX_MAX_DOPS bytes per slot
 
+// The (N_RX, N_eff_TX) pairs a receiver's kernels are instantiated for. Each receiver writes its set once, as an
+// rx_pairs type next to its launcher; the launcher and the *_supported predicate both go through rx_pair_dispatch.
+template <int R, int T>
+struct rx_pair {};
+template <class... P>
+struct rx_pairs {};
+// f(R, T) as std::integral_constants for the pair of the set that equals (r, t); false: the set has no such pair
+template <int... R, int... T, class F>
+inline bool rx_pair_dispatch(rx_pairs<rx_pair<R, T>...>, uint32_t r, uint32_t t, F&& f) {
+    return ((r == R && t == T ? (f(std::integral_constant<int, R>{}, std::integral_constant<int, T>{}), true) : false) || ...);
+}
+template <class S>
+inline bool rx_pair_in(S set, uint32_t r, uint32_t t) {
+    return rx_pair_dispatch(set, r, t, [](auto, auto) {});
+}
+
 // back end, see geometry.hpp rx_plan_t (identical layouts)
 struct rx_seg {
     uint32_t kind, l, j0, j1, mode, rel, swap, off, drs_cnt, u0, twin;
@@ -225,61 +245,55 @@ struct rx_epoch {
     uint32_t seg0, seg1, units;
 };
 
-struct rx_snr_args {        // DRS zero-forcing SNR chain + LUT profile picks, one WG per packet
+// A phase's DRS ops as the kernels that walk them once per packet see them (rx_drs.hip; host: rx.cpp drs_view)
+struct rx_drs_view {
     uint32_t N_RX, Nf_pad, n_sym_total, n_drs, n_dops, is_pdc;
     const uint32_t* dl;     // per DRS op: symbol
-    const uint32_t* dmeta;  // per DRS op: ts_first | ts_last << 8 | parity << 16
+    const uint32_t* dmeta;  // per DRS op: ts_first | ts_last << 8 | parity << 16 (drs_op_of)
     const uint32_t* drs_k;  // [2][4][n_drs]
     const float* drs_v;     // [8][n_drs]
-    float prof_snr[3];
     const float2* Y;
     rx_pkt_state* st;
+    const uint32_t* sel;    // launch packet -> slot / output row
+};
+struct drs_op {
+    uint32_t tf, tl, par;   // ts_first, ts_last, parity
+};
+__host__ __device__ __forceinline__ drs_op drs_op_of(uint32_t meta) {
+    return {meta & 0xFFu, (meta >> 8) & 0xFFu, (meta >> 16) & 0xFFu};
+}
+
+struct rx_snr_args {        // DRS zero-forcing SNR chain + LUT profile picks, one WG per packet
+    rx_drs_view V;
+    float prof_snr[3];
     uint8_t* lut_d;         // [slot][RX_MAX_DOPS]: profile picked after each DRS op
     float* nv_d;            // [slot][RX_MAX_DOPS]: noise variance per RX cell after each DRS op
-    const uint32_t* sel;    // launch packet -> slot / output row
     const double2* snr_part;  // front-end partial sums (rx_front_args::snr_part) or null: gather from Y
 };
 hipError_t launch_rx_snr(const rx_snr_args& a, uint32_t n, hipStream_t st);
 
-// Residual STO from the DRS symbols (estimator_sto.cpp:64-97, 148-171), one WG per packet: the phase
-// plan's DRS ops in order, each measured on Y rows the front end derotated with the STF increment alone,
-// and the per-symbol table the front ends then derotate with (rx_front_args::sto_sym)
-struct rx_sto_args {
-    uint32_t N_RX, Nf_pad, n_sym_total, n_drs, n_dops, N_occ, is_pdc;
+// The two residual trackers, one WG per packet each: the phase plan's DRS ops in order, measured on Y rows the
+// front end derotated and mixed with the STF values alone, and the per-symbol table the front ends then take.
+//  STO (estimator_sto.cpp:64-97, 148-171): rx_front_args::sto_sym.
+//  CFO (the intent of RX_SYNCED_PARAM_CFO_RESIDUAL_BASED_ON_DRS, rx_synced_param.hpp:162-181): each op compared
+//  with the latest earlier op of the same stream set; rx_front_args::cfo_sym.
+constexpr uint32_t RX_CFO_KEEP = 2;  // PCC-phase DRS ops whose pilots are kept for the PDC phase's first pairs
+struct rx_track_args {      // what both take
+    rx_drs_view V;
     uint32_t sym_first, sym_last;  // the phase's symbols: the table entries it fills (the PCC phase from the STF, 0)
-    double gain;            // scales each residual before it is added to the running increment
-    const uint32_t* dl;     // the phase plan's DRS ops (rx_snr_args)
-    const uint32_t* dmeta;
-    const uint32_t* drs_k;
-    const float* drs_v;
-    const float2* Y;
-    rx_pkt_state* st;
-    const uint32_t* sel;    // launch packet -> slot / output row
+    double gain;            // scales each residual before it changes the running increment
+};
+struct rx_sto_args : rx_track_args {
+    uint32_t N_occ;
     double* tab;            // [slot][n_sym_total]
 };
-hipError_t launch_rx_sto_track(const rx_sto_args& a, uint32_t n, hipStream_t st);
-
-// Residual CFO from the DRS symbols (the intent of RX_SYNCED_PARAM_CFO_RESIDUAL_BASED_ON_DRS,
-// rx_synced_param.hpp:162-181), one WG per packet: the phase plan's DRS ops in order, each compared with the
-// latest earlier op of the same stream set on Y rows the front end mixed with the STF values alone, and the
-// per-symbol mixer table the front ends then take (rx_front_args::cfo_sym)
-constexpr uint32_t RX_CFO_KEEP = 2;  // PCC-phase DRS ops whose pilots are kept for the PDC phase's first pairs
-struct rx_cfo_args {
-    uint32_t N_RX, Nf_pad, n_sym_total, n_drs, n_dops, is_pdc;
-    uint32_t sym_first, sym_last;  // the phase's symbols: the table entries it fills (the PCC phase from the STF, 0)
-    uint32_t n_stf, sym_len, Nd;   // STF_CP + N_b_DFT_os, CP + N_b_DFT_os, N_b_DFT_os (DECT-rate samples)
-    double gain;            // scales each residual before it is taken off the running increment
-    const uint32_t* dl;     // the phase plan's DRS ops (rx_snr_args)
-    const uint32_t* dmeta;
-    const uint32_t* drs_k;
-    const float* drs_v;
-    const float2* Y;
+struct rx_cfo_args : rx_track_args {
+    uint32_t n_stf, sym_len, Nd;  // STF_CP + N_b_DFT_os, CP + N_b_DFT_os, N_b_DFT_os (DECT-rate samples)
     const rx_pkt_in* pin;
-    rx_pkt_state* st;
-    const uint32_t* sel;    // launch packet -> slot / output row
     double2* tab;           // [slot][n_sym_total]
     float2* keep;           // [slot][RX_CFO_KEEP][N_RX][4][n_drs]: zero-forced pilots of the PCC phase's ops
 };
+hipError_t launch_rx_sto_track(const rx_sto_args& a, uint32_t n, hipStream_t st);
 hipError_t launch_rx_cfo_track(const rx_cfo_args& a, uint32_t n, hipStream_t st);
 
 struct rx_lut {             // one Wiener LUT: [T][4][Nf] pilot | weight << 16, weights [n_vec][n]
@@ -317,6 +331,7 @@ struct rx_cells_args {      // equalisation + demapping, one WG per (packet, epo
     uint32_t llr_stride;
     const uint32_t* sel;            // launch packet -> slot / output row
 };
+bool rx_cells_supported(uint32_t N_RX, uint32_t NT, bool sm);  // instantiated (N_RX, N_eff_TX) pairs
 hipError_t launch_rx_cells(const rx_cells_args& a, uint32_t n, hipStream_t st);
 
 // PDC phase per (packet, epoch) workgroup (rx_epoch.hip): the front end of the epoch's symbols
@@ -334,7 +349,7 @@ hipError_t launch_rx_epoch(const rx_epoch_args& x, uint32_t n, hipStream_t st);
 // spatial multiplexing (a.sm): N_RX x N_SS in {2, 4, 8} x {2, 4} with N_RX >= N_SS
 hipError_t launch_rx_cells_sm(const rx_cells_args& a, uint32_t n, hipStream_t st);
 
-// rx_cells_kernel's per-workgroup LDS staging (rx_back.hip, rx_eq.hpp).
+// rx_cells_kernel's per-workgroup LDS staging (rx_cells.hip, rx_eq.hpp).
 // The epoch's pilot buffer zfi: one row per (rx, ts) of 2 nd interlaced pilots plus ZFI_PAD zeros (a
 // union window may run past a row's last pilot). Rows start on the same bank (stride a multiple of 32
 // float2 = 64 dwords): a wave's lanes take consecutive SFBC pairs, whose streams alternate between

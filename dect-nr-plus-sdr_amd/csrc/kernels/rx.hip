@@ -7,7 +7,7 @@
 //  rx_fft_kernel   one WG per (packet, antenna, symbol block): resampling + phase-continuous mixer
 //                  + CP removal + FFT + bin extraction + amplitude scaling + STO derotation
 //                  (rx_synced.cpp:711-771) into the frequency-domain grid Y in HBM.
-// The back end (channel estimation, equalisation, demapping) is in rx_back.hip.
+// The back end (channel estimation, equalisation, demapping) is in rx_drs.hip, rx_cells.hip and rx_mimo.hip.
 #include "device_common.hpp"
 #include "experiments.hpp"
 #include "kernels.hpp"
@@ -528,20 +528,20 @@ static size_t rx_stf_lds(rx_front_args& a) {
     const bool ct = a.stream && a.L == 9 && a.M == 10 && a.hl == 24;
     if (ct && lgN % 2 == 0 && a.STF_CP >= Nd + Nd / 32) return size_t(std::max(rx_stf_area(n_stf), n_stf)) * sizeof(float2);
     const size_t whole = (n_stf + rx_stf_in(n_stf, Nd, a.M, a.L, a.hl)) * sizeof(float2) + taps;
-    if (whole <= 160 * 1024 || Nd > 8192) return whole;
+    if (whole <= LDS_BYTES || Nd > 8192) return whole;
     a.stf_chunk = 2048;
     return rx_stf_chunk_taps(n_stf, Nd, a.stf_chunk, a.M, a.L, a.hl) * sizeof(float2) + taps;
 }
 
 bool rx_front_fits(const rx_front_args& a_in) {  // every RX front-end launch of the geometry fits the LDS
     rx_front_args a = a_in;
-    return rx_stf_lds(a) <= 160 * 1024 && (rx_fft_wave_path(a) || rx_fft_layout(a));
+    return rx_stf_lds(a) <= LDS_BYTES && (rx_fft_wave_path(a) || rx_fft_layout(a));
 }
 
 hipError_t launch_rx_stf(const rx_front_args& a_in, uint32_t n, hipStream_t st) {
     rx_front_args a = a_in;
     const size_t lds = rx_stf_lds(a);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > LDS_BYTES) return hipErrorInvalidValue;
     if (a.stf_chunk)  // N_b_DFT_os = 8192: the chunked layout, run-time taps
         hipLaunchKernelGGL((rx_stf_ant_kernel<-1, false, true>), dim3(n * a.N_RX), dim3(256), lds, st, a);
     else if (a.stream && a.L == 9 && a.M == 10 && a.hl == 24)  // compiled-in taps (table taps: 0.50 vs 0.38 ms, docs/DESIGN_LOG.md §6)
@@ -774,7 +774,7 @@ static size_t rx_fft_lds(const rx_front_args& a, uint32_t pass, bool tw_lds) {
 static bool rx_fft_layout(rx_front_args& a) {
     for (uint32_t pass = RX_SYM_PASS; pass >= 1; --pass)
         for (int tw = 1; tw >= 0; --tw)
-            if (rx_fft_lds(a, pass, tw) <= 160 * 1024) {
+            if (rx_fft_lds(a, pass, tw) <= LDS_BYTES) {
                 a.fft_pass = pass;
                 a.fft_tw_lds = static_cast<uint32_t>(tw);
                 return true;

@@ -3,7 +3,7 @@
 // The Y path runs the front end over every PDC symbol of the batch (rx_fft_wave_ct_kernel), stores the
 // occupied bins to Y in HBM and reads them back in rx_cells_kernel one launch later: 35 GB written and
 // read again per 16384-slot C4 chunk. Here one workgroup owns a (packet, epoch) -- an epoch is the run
-// of cell work over one interlaced pilot buffer (rx_back.hip) -- and
+// of cell work over one interlaced pilot buffer (rx_cells.hip) -- and
 //   1. its 8 wavefronts run the front end of the epoch's symbols for every RX antenna (the wave
 //      front end of rx.hip: span staged in the wave's LDS region, 9/10 polyphase with compile-time
 //      taps + mixer, wave_fft1024, amplitude and STO derotation), the bins stored to the packet's Y
@@ -244,9 +244,10 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
     }
 }
 
-bool rx_epoch_supported(uint32_t N_RX, uint32_t NT) {
-    return (NT == 1 && (N_RX == 1 || N_RX == 2 || N_RX == 4)) || (NT == 2 && (N_RX == 2 || N_RX == 4)) || (NT == 4 && N_RX == 4);
-}
+// the instantiated (N_RX, N_eff_TX) pairs
+using epoch_pairs = rx_pairs<rx_pair<1, 1>, rx_pair<2, 1>, rx_pair<4, 1>, rx_pair<2, 2>, rx_pair<4, 2>, rx_pair<4, 4>>;
+
+bool rx_epoch_supported(uint32_t N_RX, uint32_t NT) { return rx_pair_in(epoch_pairs{}, N_RX, NT); }
 
 size_t rx_epoch_lds(const rx_cells_args& a) {
     return std::max(ep_front_lds(), cell_lds_bytes(a.N_RX, a.NT, a.n_drs, a.wcap[0], a.wcap[1]));
@@ -255,25 +256,17 @@ size_t rx_epoch_lds(const rx_cells_args& a) {
 hipError_t launch_rx_epoch(const rx_epoch_args& x, uint32_t n, hipStream_t st) {
     const rx_cells_args& a = x.C;
     const size_t lds = rx_epoch_lds(a);
-    if (lds > 160 * 1024 || a.n_pkt != n || x.F.plan.N != 1024 || !rx_epoch_supported(a.N_RX, a.NT)) return hipErrorInvalidValue;
+    if (lds > LDS_BYTES || a.n_pkt != n || x.F.plan.N != 1024 || !rx_epoch_supported(a.N_RX, a.NT)) return hipErrorInvalidValue;
     if (x.F.S_in > ROW_SPAN_MAX || !y_rows_fit(a)) return hipErrorInvalidValue;  // the row descriptors' ranges
     const dim3 g((n + 7) / 8 * 8 * a.n_epochs), b(EP_THREADS);
-#define DNRP_EP(R, T)                                                                   \
-    if (a.N_RX == R && a.NT == T) {                                                     \
-        if (a.N_bps == 8)                                                               \
-            hipLaunchKernelGGL((rx_epoch_kernel<R, T, 8>), g, b, lds, st, x);           \
-        else                                                                            \
-            hipLaunchKernelGGL((rx_epoch_kernel<R, T, 0>), g, b, lds, st, x);           \
-        return hipGetLastError();                                                       \
-    }
-    DNRP_EP(1, 1)
-    DNRP_EP(2, 1)
-    DNRP_EP(4, 1)
-    DNRP_EP(2, 2)
-    DNRP_EP(4, 2)
-    DNRP_EP(4, 4)
-#undef DNRP_EP
-    return hipErrorInvalidValue;
+    const bool hit = rx_pair_dispatch(epoch_pairs{}, a.N_RX, a.NT, [&](auto r, auto t) {
+        constexpr int R = decltype(r)::value, T = decltype(t)::value;
+        if (a.N_bps == 8)
+            hipLaunchKernelGGL((rx_epoch_kernel<R, T, 8>), g, b, lds, st, x);
+        else
+            hipLaunchKernelGGL((rx_epoch_kernel<R, T, 0>), g, b, lds, st, x);
+    });
+    return hit ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace dnrp::dev

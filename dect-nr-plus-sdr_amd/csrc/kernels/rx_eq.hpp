@@ -1,4 +1,4 @@
-// Per-cell back end of the synchronised receiver (rx_cells_kernel, rx_back.hip): Wiener interpolation
+// Per-cell back end of the synchronised receiver (rx_cells_kernel, rx_cells.hip): Wiener interpolation
 // of the channel from the interlaced pilot buffer (rx_synced.cpp:893-949), MRC (1204-1306) or SFBC
 // combining (1335-1392), srsRAN-style int16 soft demapping and descrambling (pcc_enc.cpp:297,
 // pdc_enc.cpp:339-344).
@@ -773,7 +773,7 @@ __device__ __forceinline__ void build_pilots(const rx_cells_args& A, const rx_ep
         for (int o = 0; o < 2; ++o) {
             ok[t][o] = src[t][o] != 0xFFFFu;
             const uint32_t op = ok[t][o] ? src[t][o] : 0u;
-            const uint32_t par = A.n_dops ? (A.dmeta[op] >> 16) & 0xFFu : 0u, l = A.n_dops ? A.dl[op] : 0u;
+            const uint32_t par = A.n_dops ? drs_op_of(A.dmeta[op]).par : 0u, l = A.n_dops ? A.dl[op] : 0u;
             kb[t][o] = ok[t][o] ? par * 4 + (t & 3u) : (t & 3u);
             yo[t][o] = ok[t][o] ? l * A.Nf_pad : 0u;
         }
@@ -820,7 +820,7 @@ __device__ __forceinline__ void pilot_offsets(const rx_cells_args& A, const rx_e
         const uint32_t src = po ? s1 : s0;
         const bool ok = src != 0xFFFFu;
         const uint32_t op = ok ? src : 0u;
-        const uint32_t par = A.n_dops ? (A.dmeta[op] >> 16) & 0xFFu : 0u, l = A.n_dops ? A.dl[op] : 0u;
+        const uint32_t par = A.n_dops ? drs_op_of(A.dmeta[op]).par : 0u, l = A.n_dops ? A.dl[op] : 0u;
         const uint32_t kb = ok ? par * 4 + (t & 3u) : (t & 3u), yo = ok ? l * A.Nf_pad : 0u;
         pok |= ok ? 1u << t : 0u;
         pdv[t] = A.drs_v[t * nd + pi];

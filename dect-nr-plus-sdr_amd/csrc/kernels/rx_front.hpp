@@ -186,8 +186,7 @@ __device__ __forceinline__ void rx_drs_partials(const rx_front_args& A, uint32_t
     l = __builtin_amdgcn_readfirstlane(l);
     for (uint32_t d = __builtin_amdgcn_readfirstlane(d0); d < A.n_dops; ++d) {  // ops of a symbol: consecutive
         if (dl[d] != l) break;
-        const uint32_t meta = dm[d];
-        const uint32_t tf = meta & 0xFFu, tl = (meta >> 8) & 0xFFu, par = (meta >> 16) & 0xFFu;
+        const auto [tf, tl, par] = drs_op_of(dm[d]);
         // per lane at most 4 (nd <= 256) terms per stream: float sums, double across the lanes; the
         // right neighbour of cell i comes from the next lane (lane 63: the next round's first cell)
         float f1 = 0.f, f2 = 0.f;
@@ -203,7 +202,7 @@ __device__ __forceinline__ void rx_drs_partials(const rx_front_args& A, uint32_t
                 if (i + 1 < nd) f2 += cnorm(csub(v, vn));
             }
         double s1 = f1, s2 = f2;
-        for (int o = 32; o > 0; o >>= 1) {
+        for (int o = 32; o > 0; o >>= 1) {  // not wave_sum2: it changes rx_fft_wave_ct_kernel<2>'s register allocation
             s1 += __shfl_xor(s1, o);
             s2 += __shfl_xor(s2, o);
         }

@@ -351,9 +351,11 @@ __global__ void __launch_bounds__(64 * NRX) __attribute__((amdgpu_waves_per_eu(N
     }
 }
 
-bool rx_fused_supported(uint32_t N_RX, uint32_t NT) {
-    return (N_RX == 1 || N_RX == 2 || N_RX == 4 || N_RX == 8) && (NT == 1 || NT == 2 || NT == 4) && NT <= N_RX;
-}
+// the instantiated (N_RX, N_eff_TX) pairs
+using fused_pairs = rx_pairs<rx_pair<1, 1>, rx_pair<2, 1>, rx_pair<4, 1>, rx_pair<8, 1>, rx_pair<2, 2>, rx_pair<4, 2>,
+                             rx_pair<8, 2>, rx_pair<4, 4>, rx_pair<8, 4>>;
+
+bool rx_fused_supported(uint32_t N_RX, uint32_t NT) { return rx_pair_in(fused_pairs{}, N_RX, NT); }
 
 size_t rx_fused_lds(uint32_t N_RX) { return size_t(N_RX) * fused_region() * sizeof(float2); }
 
@@ -362,23 +364,11 @@ hipError_t launch_rx_fused(const rx_fused_args& a, hipStream_t st) {
         return hipErrorInvalidValue;
     const dim3 g((a.n_pkt + 7) / 8 * 8 * a.n_fsym), b(64 * a.F.N_RX);
     const size_t lds = rx_fused_lds(a.F.N_RX);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-#define DNRP_FUSED(R, T)                                                   \
-    if (a.F.N_RX == R && a.NT == T) {                                      \
-        hipLaunchKernelGGL((rx_fused_kernel<R, T>), g, b, lds, st, a);     \
-        return hipGetLastError();                                          \
-    }
-    DNRP_FUSED(1, 1)
-    DNRP_FUSED(2, 1)
-    DNRP_FUSED(4, 1)
-    DNRP_FUSED(8, 1)
-    DNRP_FUSED(2, 2)
-    DNRP_FUSED(4, 2)
-    DNRP_FUSED(8, 2)
-    DNRP_FUSED(4, 4)
-    DNRP_FUSED(8, 4)
-#undef DNRP_FUSED
-    return hipErrorInvalidValue;
+    if (lds > LDS_BYTES) return hipErrorInvalidValue;
+    rx_pair_dispatch(fused_pairs{}, a.F.N_RX, a.NT, [&](auto r, auto t) {  // a pair of the set: checked above
+        hipLaunchKernelGGL((rx_fused_kernel<decltype(r)::value, decltype(t)::value>), g, b, lds, st, a);
+    });
+    return hipGetLastError();
 }
 
 }  // namespace dnrp::dev

@@ -772,7 +772,7 @@ bool sync_peak_ok(const sync_args& a) {  // the grid layout's preconditions (eve
     const bool staged_ok = sync_class_of(a) != SYNC_CLASS_9_10_24 ||
                            (nb <= 2 * 512 && size_t(n_in) * sizeof(float2) <= sync_peak_lds(a) - SYNC_SHARED_F2 * sizeof(float2));
     return a.D % 8 == 0 && a.pattern % 8 == 0 && (a.stf_len + SYNC_PAD_PEAK) % 8 == 0 && a.D / 8 <= 512 &&
-           (a.n_uw == 6 || a.n_uw == 8) && sync_peak_lds(a) <= 160 * 1024 && staged_ok;
+           (a.n_uw == 6 || a.n_uw == 8) && sync_peak_lds(a) <= LDS_BYTES && staged_ok;
 }
 
 hipError_t launch_sync_peak(const sync_args& a, uint32_t n, hipStream_t st) {

@@ -404,7 +404,7 @@ size_t sync_post_lds(const sync_args& a) {  // the staged form's input span (n_i
 hipError_t launch_sync_post(const sync_args& a, uint32_t n, hipStream_t st) {
     const dim3 g(n * a.max_reports * a.n_ant);
     const size_t lds = sync_post_lds(a);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > LDS_BYTES) return hipErrorInvalidValue;
     auto go = [&](auto l, auto m, auto h, auto ct) {
         hipLaunchKernelGGL((sync_post_kernel<decltype(l)::value, decltype(m)::value, decltype(h)::value, decltype(ct)::value>), g,
                            dim3(SYNC_THREADS), lds, st, a);
@@ -416,7 +416,7 @@ hipError_t launch_sync_post(const sync_args& a, uint32_t n, hipStream_t st) {
 hipError_t launch_sync_beta(const sync_args& a, const sync_beta_args& ba, uint32_t n, hipStream_t st) {
     const dim3 g(n * a.max_reports * a.n_ant);
     const size_t lds = (12 + 2 * size_t(ba.plan.N)) * sizeof(float2);
-    if (lds > 160 * 1024 || ba.cp + ba.plan.N != a.stf_len) return hipErrorInvalidValue;
+    if (lds > LDS_BYTES || ba.cp + ba.plan.N != a.stf_len) return hipErrorInvalidValue;
     sync_dispatch<true>(a, [&](auto l, auto m, auto h, auto ct) {  // compiled-in 9/10 taps, as sync_post_kernel
         hipLaunchKernelGGL((sync_beta_kernel<decltype(l)::value, decltype(m)::value, decltype(h)::value, decltype(ct)::value>), g,
                            dim3(SYNC_THREADS), lds, st, a, ba);
@@ -431,7 +431,7 @@ size_t sync_fine_lds(const sync_args& a) { return sync_fine_layout(a.log2_fft, D
 // the oracle, so it stays declined.
 bool sync_fine_ok(const sync_args& a) {
     const size_t two = (16 + 2 * (size_t(1) << a.log2_fft)) * sizeof(float2);
-    return std::max(two, sync_fine_lds(a)) <= 160 * 1024;
+    return std::max(two, sync_fine_lds(a)) <= LDS_BYTES;
 }
 
 hipError_t launch_sync_fine(const sync_args& a, uint32_t n, hipStream_t st) {

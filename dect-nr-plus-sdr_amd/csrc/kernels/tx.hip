@@ -1354,7 +1354,7 @@ hipError_t launch_tx(const tx_args& a, uint32_t n, hipStream_t st) {
         const uint32_t total = a.STF_CP + a.N_DF * a.CP + (a.N_DF + 1) * a.plan.N;
         if (total > a.big_len) return hipErrorInvalidValue;
         const size_t lds = (2 * size_t(a.plan.N) + 256 + 98 + 8) * sizeof(float2);
-        if (lds > 160 * 1024 || a.big_batch == 0) return hipErrorInvalidValue;
+        if (lds > LDS_BYTES || a.big_batch == 0) return hipErrorInvalidValue;
         // passes of big_batch packets through the scratch (the host caps its size), each pass with
         // the packet-indexed arguments offset to its first packet; the largest pass's grids checked
         // before the first launch, so a call either runs every pass or none

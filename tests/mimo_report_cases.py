@@ -1,6 +1,6 @@
 """Inputs and the model shared by tests/test_rx_mimo_report_host.py and tests/test_gpu_rx_mimo_report.py (TEST
 INFRASTRUCTURE, no GPU): the MIMO report options (dnrp_ctx_set_rx_mimo_report, dnrp_rx_mimo_detail;
-kernels/rx_back.hip rx_mimo_detail_kernel).
+kernels/rx_mimo.hip rx_mimo_detail_kernel).
 
 The model restates, in double precision numpy, the single-stream codebook search of estimator_mimo.cpp:162-271
 under its three metrics and both search starts (search()), and the rank / precoder report for spatial

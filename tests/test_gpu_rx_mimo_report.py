@@ -1,4 +1,4 @@
-"""The MIMO report options on the GPU (dnrp_ctx_set_rx_mimo_report, dnrp_rx_mimo_detail; kernels/rx_back.hip
+"""The MIMO report options on the GPU (dnrp_ctx_set_rx_mimo_report, dnrp_rx_mimo_detail; kernels/rx_mimo.hip
 rx_mimo_detail_kernel). Inputs and the numpy model: tests/mimo_report_cases.py, its proof against hand-computed
 examples and the conditions on the seeds: tests/test_rx_mimo_report_host.py.
 
@@ -23,13 +23,14 @@ import mimo_report_cases as MR
 import oracle_py as O
 import phy_fixtures as F
 import rx_grid_cases as RG
+import rx_run_helpers as H
+from rx_run_helpers import clean_env as _clean_env
 
 torch = pytest.importorskip("torch")
 
 pytestmark = pytest.mark.gpu
 
 EINVAL, ESTATE = -1, -7
-_ENV = ("DNRP_RX_EPOCH", "DNRP_RX_FUSED", "DNRP_RX_SNR_FRONT", "DNRP_RX_GROUP")
 # measured on the first MI355X run (geometry: value); see the module docstring
 # scores: the largest over the six settings; rates: over the batch and, for t2r2 / t4r4, the rank-one windows (their
 # G is near singular in the second direction: 1.806e-06 / 1.173e-05; the batches alone 1.115e-07 / 6.799e-07) and the
@@ -50,39 +51,14 @@ def _bound(measured, cap):
     return cap if measured is None else min(cap, 10.0 * measured)
 
 
-def _clean_env(monkeypatch, **env):
-    for k in _ENV:
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv("DNRP_TIMING", "1")
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-
-
 def _phy(ctx, lr=1, max_batch=MR.N_PACKETS):
-    import dnrp
-    u_max, b_max, n_rx, os_min, L, M = ctx
-    phy = dnrp.Phy(u_max, b_max, n_rx, os_min, L, M, chestim_mode_lr=bool(lr), max_batch=max_batch)
-    for nid in range(100, 106):
-        phy.add_network_id(nid)
-    return phy
+    return H.phy(ctx, lr, max_batch)
 
 
 def _rx(phy, psd, windows, reports, reqs, want_report=True, detail=False):
-    """One PCC batch of all windows and one PDC batch of reqs = [(pcc_index, network_id, plcf_type)]:
-    (PDC LLRs (torch, host), PDC reports or None, detail rows or None)"""
-    import dnrp
-    ps = dnrp.psdef(*psd)
-    sz = phy.packet_sizes(ps)
-    n, n_rx, S = len(windows), phy.cfg.N_TX_max, windows[0].shape[1]
-    dev = torch.device("cuda:0")
-    iq = torch.from_numpy(np.stack(windows).view(np.float32).reshape(n, n_rx, S, 2)).to(dev)
-    pcc_llr = torch.zeros((n, 196), dtype=torch.int16, device=dev)
-    pdc_llr = torch.zeros((len(reqs), sz["G"]), dtype=torch.int16, device=dev)
-    phy.rx_pcc_batch(reports, iq, pcc_llr)
-    rep = phy.rx_pdc_batch([dnrp.PdcReq(ps, i, nid, pt) for i, nid, pt in reqs], iq, pdc_llr, want_report=want_report)
-    phy.sync()
-    rows = phy.rx_mimo_detail(len(reqs)) if detail else None
-    return pdc_llr.cpu(), rep, rows
+    """rx_run_helpers.rx as (PDC LLRs (torch, host), PDC reports or None, detail rows or None)"""
+    r = H.rx(phy, psd, windows, reports, reqs, pcc_report=False, pdc_report=want_report, detail=detail)
+    return r.pdc_llr, r.rep2, r.rows
 
 
 def _sync_reports(g, ws):
@@ -90,10 +66,7 @@ def _sync_reports(g, ws):
     return [dnrp.SyncReport(w["off"], 0.0, 0.0, g["psd"][0], g["psd"][1], g["n_ts"]) for w in ws]
 
 
-def _same_reports(a, b):
-    for x, y in zip(a, b):
-        assert (x.snr_dB, x.mimo_N_RX, x.mimo_N_TS_other, x.tm_3_7_beamforming_idx, x.tm_3_7_beamforming_reciprocal_idx) == \
-            (y.snr_dB, y.mimo_N_RX, y.mimo_N_TS_other, y.tm_3_7_beamforming_idx, y.tm_3_7_beamforming_reciprocal_idx)
+_same_reports = H.same_pdc_reports
 
 
 def _run_windows(name, ws, setting, want_report=True, reqs=None, env_phy=None):

@@ -1,5 +1,5 @@
 """Residual STO tracking from the DRS symbols on the GPU (dnrp_ctx_set_rx_sto_tracking, dnrp_rx_sto_track;
-kernels/rx_back.hip rx_sto_track_kernel, the per-symbol table through rx_fft_kernel, rx_fft_wave_kernel,
+kernels/rx_drs.hip rx_sto_track_kernel, the per-symbol table through rx_fft_kernel, rx_fft_wave_kernel,
 rx_fft_wave_ct_kernel and rx_epoch_kernel). Inputs, the numpy model and their proof against the injected
 truth: tests/sto_track_cases.py, tests/test_rx_sto_track_host.py.
 
@@ -27,14 +27,15 @@ import llr_gate
 import oracle_py as O
 import phy_fixtures as F
 import rx_grid_cases as RG
+import rx_run_helpers as H
 import sto_track_cases as ST
+from rx_run_helpers import clean_env as _clean_env, phy as _phy
 
 torch = pytest.importorskip("torch")
 
 pytestmark = pytest.mark.gpu
 
 EINVAL, EUNSUPPORTED = -1, -3
-_ENV = ("DNRP_RX_EPOCH", "DNRP_RX_FUSED", "DNRP_RX_SNR_FRONT", "DNRP_RX_GROUP")
 TABLE_CAP = 0.01
 # measured |device - model| / period on the first MI355X run (case: value); see the module docstring
 TABLE_DIFF = {"a": 1.025e-07, "b": 8.912e-08, "c": 2.374e-08, "d": 1.025e-07, "a_half": 4.342e-08}
@@ -44,48 +45,15 @@ def _table_bound(key):
     return TABLE_CAP if TABLE_DIFF[key] is None else min(TABLE_CAP, 10.0 * TABLE_DIFF[key])
 
 
-def _clean_env(monkeypatch, **env):
-    for k in _ENV:
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv("DNRP_TIMING", "1")
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-
-
-def _phy(ctx, lr=1, max_batch=4):
-    import dnrp
-    u_max, b_max, n_rx, os_min, L, M = ctx
-    phy = dnrp.Phy(u_max, b_max, n_rx, os_min, L, M, chestim_mode_lr=bool(lr), max_batch=max_batch)
-    for nid in range(100, 106):
-        phy.add_network_id(nid)
-    return phy
-
-
 def _rx(phy, psd, windows, reports, reqs, table=False):
-    """One PCC batch of all windows and one PDC batch of reqs = [(pcc_index, network_id, plcf_type)]:
-    (PCC LLRs, PDC LLRs (torch, host), PCC reports, PDC reports, table or None)"""
-    import dnrp
-    ps = dnrp.psdef(*psd)
-    sz = phy.packet_sizes(ps)
-    n, n_rx, S = len(windows), phy.cfg.N_TX_max, windows[0].shape[1]
-    dev = torch.device("cuda:0")
-    iq = torch.from_numpy(np.stack(windows).view(np.float32).reshape(n, n_rx, S, 2)).to(dev)
-    pcc_llr = torch.zeros((n, 196), dtype=torch.int16, device=dev)
-    pdc_llr = torch.zeros((len(reqs), sz["G"]), dtype=torch.int16, device=dev)
-    rep1 = phy.rx_pcc_batch(reports, iq, pcc_llr, want_report=True)
-    rep2 = phy.rx_pdc_batch([dnrp.PdcReq(ps, i, nid, pt) for i, nid, pt in reqs], iq, pdc_llr, want_report=True)
-    phy.sync()
-    tab = phy.rx_sto_track(n) if table else None
-    return pcc_llr.cpu(), pdc_llr.cpu(), rep1, rep2, tab
+    """rx_run_helpers.rx as (PCC LLRs, PDC LLRs (torch, host), PCC reports, PDC reports, table or None)"""
+    r = H.rx(phy, psd, windows, reports, reqs, sto_table=table)
+    return r.pcc_llr, r.pdc_llr, r.rep1, r.rep2, r.sto_tab
 
 
 def _same_reports(a1, a2, b1, b2):
-    for x, y in zip(a1, b1):
-        assert (x.snr_dB, x.cfo_fractional_rad, x.sto_fractional, list(x.rms)) == \
-            (y.snr_dB, y.cfo_fractional_rad, y.sto_fractional, list(y.rms))
-    for x, y in zip(a2, b2):
-        assert (x.snr_dB, x.mimo_N_RX, x.mimo_N_TS_other, x.tm_3_7_beamforming_idx, x.tm_3_7_beamforming_reciprocal_idx) == \
-            (y.snr_dB, y.mimo_N_RX, y.mimo_N_TS_other, y.tm_3_7_beamforming_idx, y.tm_3_7_beamforming_reciprocal_idx)
+    H.same_pcc_reports(a1, b1)
+    H.same_pdc_reports(a2, b2)
 
 
 _PAR = {}

@@ -20,9 +20,9 @@ import rx_grid_cases as G
 
 dnrp = pytest.importorskip("dnrp")
 
-PAIRS_EPOCH = [(1, 1), (2, 1), (4, 1), (2, 2), (4, 2), (4, 4)]                          # rx_epoch.hip DNRP_EP
-PAIRS_ALL = [(1, 1), (2, 1), (4, 1), (8, 1), (2, 2), (4, 2), (8, 2), (4, 4), (8, 4)]    # DNRP_FUSED, DNRP_CELLS
-PAIRS_SM = [(2, 2), (4, 2), (8, 2), (4, 4), (8, 4)]                                     # DNRP_CELLS_SM
+PAIRS_EPOCH = [(1, 1), (2, 1), (4, 1), (2, 2), (4, 2), (4, 4)]                          # rx_epoch.hip epoch_pairs
+PAIRS_ALL = [(1, 1), (2, 1), (4, 1), (8, 1), (2, 2), (4, 2), (8, 2), (4, 4), (8, 4)]    # fused_pairs, cells_pairs
+PAIRS_SM = [(2, 2), (4, 2), (8, 2), (4, 4), (8, 4)]                                     # cells_sm_pairs
 
 # every instantiation the four launchers can take: (receiver, N_RX, N_eff_TX, NBPS class)
 CLASSES = (
