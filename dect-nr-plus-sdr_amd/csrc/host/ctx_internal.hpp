@@ -281,7 +281,8 @@ struct sync_tables {  // per (u, b) of the searched STF: sync_chunk_t / crosscor
     dbuf taps, taps_pp, tmpl_f, tw_fft;
     // beta search (dnrp_ctx_set_sync_beta_search), built at its first use for this (u, b): template
     // spectra [b_idx][n_templates][n_fft] of every b <= this b, plan and twiddles of the 64 bos-point transform
-    bool beta_ready = false;
+    // (plan and twiddles: coarse_fft_ready, shared with the integer CFO search)
+    bool beta_ready = false, coarse_fft_ready = false;
     dbuf tmpl_fb, tw_beta;
     dev::fft_plan beta_plan{};
 };
@@ -379,6 +380,12 @@ struct dnrp_ctx {
     uint32_t sync_fine_all = 0;
     uint32_t sync_fine_reports = 0;
     dbuf sy_fine_m, sy_fine_i;
+    // integer CFO search at the coarse peak (dnrp_ctx_set_sync_icfo_search): 0 = off, or the candidate range of
+    // later sync calls; sy_icfo: the score table [n * max_reports][8][9] of the latest dnrp_rx_sync_batch that ran
+    // with it on, sync_icfo_reports its n * max_reports (0: none, or it ran off), sync_icfo_ant its antennas
+    uint32_t sync_icfo_range = 0;
+    uint32_t sync_icfo_reports = 0, sync_icfo_ant = 0;
+    dbuf sy_icfo;
     // ring-buffer gather / continuous-stream synchronisation (stream.cpp)
     dbuf ring_start, ring_win;
     pinned st_ring, st_stream;

@@ -224,6 +224,17 @@ int dnrp_query_table(const char* name, const uint32_t* arg, uint32_t n_arg, floa
             host::read_sync(sw);
             for (const uint32_t f : geo::sync_tranches(a(0), a(1), a(2), a(3), a(4), sw.sync_tranche_set ? &sw.sync_tranche : nullptr))
                 v.push_back(static_cast<float>(f));
+        } else if (n == "sync_icfo_cells") {  // (N, b, k as int32): the bins, mod N, whose power candidate k of the
+            // integer CFO search sums (sync_icfo_kernel): 4 (i + k), 0 < |i| <= N_b_OCC(b) / 8, i ascending; empty
+            // for a candidate that is not searched (its cells would reach N / 2). N = 64 b_max os_min: a multiple of 64, at least 64 b
+            if (n_arg != 3) return DNRP_EINVAL;
+            const bool bok = a(1) == 1 || a(1) == 2 || a(1) == 4 || a(1) == 8 || a(1) == 12 || a(1) == 16;
+            if (!bok || a(0) % 64 || a(0) < 64 * a(1) || a(0) > (1u << 20)) return DNRP_EINVAL;
+            const int32_t k = static_cast<int32_t>(a(2)), N = static_cast<int32_t>(a(0)), h = 7 * static_cast<int32_t>(a(1));
+            if (std::abs(k) > static_cast<int32_t>(dev::SYNC_ICFO_MAX)) return DNRP_EINVAL;
+            if (4 * (h + std::abs(k)) < N / 2)
+                for (int32_t i = -h; i <= h; ++i)
+                    if (i != 0) v.push_back(static_cast<float>(((4 * (i + k)) % N + N) % N));
         } else if (n == "sync_template") {  // (u, b_max, os_min, L, M, b, N_eff_TX): the fine search's time-domain
             // STF template of a b packet in a b_max stream, tmpl_len hw samples re/im (stf_template.cpp:93-199)
             auto listed = [](uint32_t b) { return b == 1 || b == 2 || b == 4 || b == 8 || b == 12 || b == 16; };

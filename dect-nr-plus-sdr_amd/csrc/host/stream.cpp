@@ -169,6 +169,7 @@ int dnrp_rx_sync_stream(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, const float* rin
     err = dnrp_rx_sync_batch(ctx, sc, n_chunks, ctx->ring_win.as<float>(), uint64_t(N_ant) * S_win, S_win, S_win, res, cnt,
                              stream);
     ctx->sync_fine_reports = 0;  // dnrp_rx_sync_fine_peaks is not offered here: the reports below are filtered
+    ctx->sync_icfo_reports = 0;  // nor dnrp_rx_sync_icfo_scores
     if (err != DNRP_OK) return err;
     HIPCHK(hipEventRecord(ctx->st_stream.ev, st));
     HIPCHK(hipStreamSynchronize(st));

@@ -118,11 +118,23 @@ void template_spectrum(uint32_t u, uint32_t b_max, uint32_t os, const geo::resam
 // b_idx2b (physical_resources.hpp): the packet bandwidths, ascending
 constexpr uint32_t B_IDX2B[6] = {1, 2, 4, 8, 12, 16};
 
+// the N_b_DFT_os-point transform at the coarse peak (coarse_peak_f_domain.cpp:55), first use for this
+// (u, b_max) by the beta search or the integer CFO search: plan and twiddles
+bool ensure_coarse_fft(sync_tables* t) {
+    if (t->coarse_fft_ready) return true;
+    const uint32_t N = prm::N_SAMPLES_STF_PATTERN * 4 * t->bos;  // 64 b_max os
+    t->beta_plan = make_plan(N);
+    if (!t->tw_beta.upload(twiddles(N))) return false;
+    t->coarse_fft_ready = true;
+    return true;
+}
+
 // beta search (dnrp_ctx_set_sync_beta_search), first use for this (u, b_max): the template spectra of
 // every b <= b_max (stf_template.cpp:137-199; row block b_idx, the last one equal to tmpl_f) and the
-// plan and twiddles of the N_b_DFT_os-point transform at the coarse peak (coarse_peak_f_domain.cpp:55)
+// transform at the coarse peak
 bool ensure_beta(const dnrp_cfg& c, sync_tables* t) {
     if (t->beta_ready) return true;
+    if (!ensure_coarse_fft(t)) return false;
     const uint32_t nf = 1u << t->log2_fft;
     const auto rs_tx = geo::make_resampler(c.L, c.M, c.os_min, prm::RS_TX);
     uint32_t nb = 0;
@@ -131,9 +143,7 @@ bool ensure_beta(const dnrp_cfg& c, sync_tables* t) {
     for (uint32_t bi = 0; bi < nb; ++bi)
         for (uint32_t k = 0; k < t->n_templates; ++k)
             template_spectrum(t->u, t->b, c.os_min, rs_tx, B_IDX2B[bi], 1u << k, nf, &tf[(size_t(bi) * t->n_templates + k) * nf]);
-    const uint32_t N = prm::N_SAMPLES_STF_PATTERN * 4 * t->bos;  // 64 b_max os
-    t->beta_plan = make_plan(N);
-    if (!t->tmpl_fb.upload(tf) || !t->tw_beta.upload(twiddles(N))) return false;
+    if (!t->tmpl_fb.upload(tf)) return false;
     t->beta_ready = true;
     return true;
 }
@@ -199,6 +209,31 @@ extern "C" int dnrp_ctx_get_sync_beta_search(const dnrp_ctx* ctx, uint32_t* on, 
     if (on) *on = ctx->sync_beta_on;
     if (threshold_db) *threshold_db = ctx->sync_beta_db;
     if (threshold_linear) *threshold_linear = beta_linear(ctx->sync_beta_db);
+    return DNRP_OK;
+}
+
+extern "C" int dnrp_ctx_set_sync_icfo_search(dnrp_ctx* ctx, uint32_t range) {
+    if (!ctx || range > dev::SYNC_ICFO_MAX) return DNRP_EINVAL;
+    ctx->sync_icfo_range = range;
+    return DNRP_OK;
+}
+
+extern "C" int dnrp_ctx_get_sync_icfo_search(const dnrp_ctx* ctx, uint32_t* range) {
+    if (!ctx) return DNRP_EINVAL;
+    if (range) *range = ctx->sync_icfo_range;
+    return DNRP_OK;
+}
+
+extern "C" int dnrp_rx_sync_icfo_scores(dnrp_ctx* ctx, uint32_t n_reports, float* score, int32_t* k, void* stream) {
+    if (!ctx || !score || !k) return DNRP_EINVAL;
+    if (ctx->sync_icfo_reports == 0) return DNRP_ESTATE;
+    if (n_reports != ctx->sync_icfo_reports) return DNRP_EINVAL;
+    (void)hipSetDevice(ctx->cfg.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t row = 8 * dev::SYNC_ICFO_COLS;
+    HIPCHK(hipMemcpyAsync(score, ctx->sy_icfo.p, size_t(n_reports) * row * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // k is decided here, on the copy, by the device's function
+    for (uint32_t r = 0; r < n_reports; ++r) k[r] = dev::sync_icfo_k(score + size_t(r) * row, ctx->sync_icfo_ant);
     return DNRP_OK;
 }
 
@@ -279,6 +314,7 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
     if (sc->max_reports == 0 || S_win == 0 || sc->chunk_len < ctx->cfg.L) return DNRP_EINVAL;
     (void)hipSetDevice(ctx->cfg.device);
     ctx->sync_fine_reports = 0;  // dnrp_rx_sync_fine_peaks: the table of this call, once it has run with the setting on
+    ctx->sync_icfo_reports = 0;  // dnrp_rx_sync_icfo_scores: likewise
     int err = DNRP_OK;
     sync_tables* t = get_sync(ctx, sc->u, sc->b, &err);
     if (!t) return err;
@@ -335,6 +371,14 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
         a.beta_thr = beta_linear(ctx->sync_beta_db);
         a.band = ctx->sy_band.as<float>();
         a.tmpl_f = t->tmpl_fb.as<float2>();
+    }
+    if (ctx->sync_icfo_range) {
+        if (!ensure_coarse_fft(t) ||
+            !ctx->sy_icfo.ensure(size_t(n) * sc->max_reports * 8 * dev::SYNC_ICFO_COLS * sizeof(float)))
+            return DNRP_ENOMEM;
+        a.icfo_range = ctx->sync_icfo_range;
+        a.icfo_N = t->beta_plan.N;
+        a.icfo = ctx->sy_icfo.as<float>();
     }
     a.fine_all = ctx->sync_fine_all;
     a.det_stage = dev::sync_detect_stage(a);
@@ -453,20 +497,45 @@ extern "C" int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32
     ctx->tic("sync_post", st);
     if (dev::launch_sync_post(a, n, st) != hipSuccess) return DNRP_EDEVICE;
     ctx->toc("sync_post", st);
-    if (a.beta_on) {  // the band powers sync_fine decides b from; off: no launch, no report field written
-        dev::sync_beta_args ba{};
+    dev::sync_beta_args ba{};
+    if (a.beta_on || a.icfo_range) {
         ba.plan = t->beta_plan;
         ba.tw = t->tw_beta.as<float2>();
         ba.band = ctx->sy_band.as<float>();
         ba.cp = a.stf_len - ba.plan.N;
+        for (uint32_t i = 0; i < 4; ++i) ba.cover[i] = COVER[t->n_pattern - 4 + i];
+    }
+    if (a.beta_on) {  // the band powers sync_fine decides b from; off: no launch, no report field written
         ctx->tic("sync_beta", st);
         if (dev::launch_sync_beta(a, ba, n, st) != hipSuccess) return DNRP_EDEVICE;
         ctx->toc("sync_beta", st);
+    }
+    if (a.icfo_range) {  // the candidate scores sync_fine decides cfo_int from; off: no launch, cfo_int stays 0
+        ctx->tic("sync_icfo", st);  // the fill counts as the search's time
+        // every row -1: reports not found and the antennas past n_ant are not visited by the kernel
+        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.icfo), 0xBF800000u,
+                                 size_t(n) * a.max_reports * 8 * dev::SYNC_ICFO_COLS, st));
+        if (dev::launch_sync_icfo(a, ba, n, st) != hipSuccess) return DNRP_EDEVICE;
+        ctx->toc("sync_icfo", st);
+        if (a.beta_on) {
+            // both searches: the first beta decision read the spectrum with the integer CFO in it, and a packet
+            // moved across a band edge looks wider than it is. The reports whose decided k is not 0 get their
+            // band powers again on the spectrum moved back by 4 k bins; sync_fine then decides b from those
+            // (sync_icfo_kernel's scores keep the first decision's cells)
+            ba.shift = 1;
+            ctx->tic("sync_beta", st);
+            if (dev::launch_sync_beta(a, ba, n, st) != hipSuccess) return DNRP_EDEVICE;
+            ctx->toc("sync_beta", st);
+        }
     }
     ctx->tic("sync_fine", st);
     if (dev::launch_sync_fine(a, n, st) != hipSuccess) return DNRP_EDEVICE;
     ctx->toc("sync_fine", st);
     if (a.fine_all) ctx->sync_fine_reports = n * a.max_reports;
+    if (a.icfo_range) {
+        ctx->sync_icfo_reports = n * a.max_reports;
+        ctx->sync_icfo_ant = a.n_ant;
+    }
     HIPCHK(hipMemcpyAsync(res, a.res, size_t(n) * a.max_reports * sizeof(dev::sync_res), hipMemcpyDeviceToHost, st));
     if (n_found) HIPCHK(hipMemcpyAsync(n_found, a.n_found, size_t(n) * 4, hipMemcpyDeviceToHost, st));
     return DNRP_OK;

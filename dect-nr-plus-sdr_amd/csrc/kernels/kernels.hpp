@@ -604,13 +604,41 @@ struct sync_args {
     uint32_t fine_all;
     float* fine_m;                             // [n * max_reports][8][4] peak metric per (antenna, template), 0 where
     uint32_t* fine_i;                          // not processed; its index relative to the search start
+    // integer CFO search at the coarse peak (the project's own estimator). icfo_range 0: r.cfo_int
+    // = 0 and no launch. 1..4: sync_icfo_kernel scores the candidates k in [-range, range] per antenna into icfo
+    // [n * max_reports][8][SYNC_ICFO_COLS] (column k + 4; -1: outside the range or not searched), and the fine
+    // search decides k (sync_icfo_decide) and pre-corrects with cfo_int = -k 4 2 pi / icfo_N
+    uint32_t icfo_range, icfo_N;               // icfo_N: 64 bos, the transform of sync_beta_args
+    float* icfo;
 };
+constexpr uint32_t SYNC_ICFO_MAX = 4, SYNC_ICFO_COLS = 2 * SYNC_ICFO_MAX + 1;
+// The integer CFO of one report from sync_icfo_kernel's table sc [8][SYNC_ICFO_COLS]: the scores summed over the
+// searched antennas in antenna order, the candidates visited 0, -1, +1, -2, ... with a strictly-greater
+// comparison (0 wins ties, and wins where nothing is searched: every sum -n_ant). Device (sync_icfo_decide) and
+// host (dnrp_rx_sync_icfo_scores) decide by this one function.
+__host__ __device__ inline int32_t sync_icfo_k(const float* sc, uint32_t n_ant) {
+    int32_t kbest = 0;
+    float best = 0.f;
+    for (uint32_t v = 0; v < SYNC_ICFO_COLS; ++v) {
+        const int32_t k = v & 1u ? -static_cast<int32_t>((v + 1) / 2) : static_cast<int32_t>(v / 2);
+        float s = 0.f;
+        for (uint32_t a = 0; a < n_ant; ++a) s += sc[a * SYNC_ICFO_COLS + k + static_cast<int32_t>(SYNC_ICFO_MAX)];
+        if (v == 0 || s > best) {
+            best = s;
+            kbest = k;
+        }
+    }
+    return kbest;
+}
 constexpr uint32_t SYNC_BANDS = 6;  // b_idx2b = {1, 2, 4, 8, 12, 16}: band i = the 32-bin half-bands [b(i-1), b(i)) on either side
 struct sync_beta_args {  // sync_beta_kernel: the N = 64 bos-point transform of the STF's last N samples
     fft_plan plan;
     const float2* tw;  // forward twiddles of N
     float* band;       // sync_args::band
     uint32_t cp;       // N_samples_STF_CP_only_os: 3/4 N (u = 1) or 5/4 N
+    float cover[4];    // sync_icfo_kernel: the cover-sequence signs of the STF's last four patterns
+    uint32_t shift;    // sync_beta_kernel's second pass with both searches on: the band powers of the reports with a
+                       // decided integer CFO k != 0 again, on the spectrum moved back by 4 k bins (0: the first pass)
 };
 struct sync_state {  // sync_detect_kernel's loop registers (autocorrelator_detection / _peak state)
     uint32_t s_cur, ignore, nrep, pend;  // pend: 0 searching, 1 coarse peak pending, 2 finished
@@ -631,6 +659,7 @@ bool sync_peak_ok(const sync_args& a);
 bool sync_taps_match(const float* h, size_t n);  // compiled-in 9/10 sync taps == run-time taps
 hipError_t launch_sync_post(const sync_args& a, uint32_t n, hipStream_t st);
 hipError_t launch_sync_beta(const sync_args& a, const sync_beta_args& ba, uint32_t n, hipStream_t st);
+hipError_t launch_sync_icfo(const sync_args& a, const sync_beta_args& ba, uint32_t n, hipStream_t st);
 hipError_t launch_sync_fine(const sync_args& a, uint32_t n, hipStream_t st);
 bool sync_fine_ok(const sync_args& a);  // the fine search's LDS fits (log2_fft)
 uint32_t sync_detect_stage(const sync_args& a);

@@ -14,7 +14,7 @@
 //                   metric-weighted coarse peak time (:311-394), skip after the peak. Windowed sums are
 //                   exact prefix differences in double (the reference keeps float running sums with
 //                   periodic re-summation). sync_peak_kernel: the same search for the split rounds.
-//  sync_fine.hip    sync_post_kernel (RMS and fractional CFO at the peak), sync_beta_kernel, and
+//  sync_fine.hip    sync_post_kernel (RMS and fractional CFO at the peak), sync_beta_kernel, sync_icfo_kernel, and
 //                   sync_fine_kernel, one WG per report: CFO pre-rotation of the strongest antenna's
 //                   hw-rate samples around the coarse peak and cross-correlation with every STF
 //                   template (crosscorrelator.cpp:80-251) as one forward FFT plus one inverse FFT per

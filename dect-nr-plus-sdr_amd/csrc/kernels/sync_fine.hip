@@ -1,4 +1,4 @@
-// Coarse-peak post-processing, beta and fine peak of the synchronisation (sync_common.hpp).
+// Coarse-peak post-processing, beta, integer CFO and fine peak of the synchronisation (sync_common.hpp).
 #include "sync_common.hpp"
 
 // ---- compile-time knobs (-D), shipped values
@@ -70,7 +70,9 @@ __global__ void __launch_bounds__(SYNC_THREADS) __attribute__((amdgpu_waves_per_
 // for: band i = the 32-bin half-bands [b_idx2b[i - 1], b_idx2b[i]) left and right of the centre. Every
 // searched antenna, with or without a valid coarse peak (estimate_beta sums all nof_antennas_limited).
 // Only the band powers leave; sync_fine_kernel sums them in antenna order and decides.
-template <int LR, int MR, int HLR, bool CT>
+// SHIFT: the second pass with both searches on (sync_beta_args::shift), a form of its own so that the beta
+// search alone runs the code it had.
+template <int LR, int MR, int HLR, bool CT, bool SHIFT>
 __global__ void __launch_bounds__(SYNC_THREADS) sync_beta_kernel(sync_args A, sync_beta_args B) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     double* red = reinterpret_cast<double*>(smem);  // [24]
@@ -80,16 +82,30 @@ __global__ void __launch_bounds__(SYNC_THREADS) sync_beta_kernel(sync_args A, sy
     const uint32_t rep = blockIdx.x / A.n_ant, a = blockIdx.x % A.n_ant, w = rep / A.max_reports;
     const sync_res* rp = A.res + rep;
     if (!rp->found) return;  // uniform: the whole workgroup leaves
+    // second pass (B.shift, launched after sync_icfo_kernel with both searches on): the reports whose decided
+    // integer CFO is k != 0 get the band powers of the spectrum moved back by 4 k bins -- the transform of the
+    // samples derotated by 4 k subcarriers, exactly -- in place of the first pass's; k = 0: nothing to redo
+    int32_t sh = 0;
+    if constexpr (SHIFT) {
+        sh = 4 * sync_icfo_k(A.icfo + size_t(rep) * 8 * SYNC_ICFO_COLS, A.n_ant);
+        if (sh == 0) return;  // uniform
+    }
     const float2* x = A.iq + w * A.win_stride + a * A.ant_stride;
     resample_direct<LR, MR, HLR, CT>(A, x, static_cast<int64_t>(rp->coarse_local) + B.cp, N, [&](uint32_t i, float2 v) { xb[i] = v; });
     __syncthreads();
     const float2* S = fft_any<-1>(xb, yb, B.tw, B.plan);
     // FFT shift: bin k sits d = k bins right of the centre (k < N / 2) or N - 1 - k bins left of it
     double p[SYNC_BANDS] = {};
-    for (uint32_t k = threadIdx.x; k < N; k += blockDim.x) {
+    for (uint32_t kb = threadIdx.x; kb < N; kb += blockDim.x) {
+        uint32_t k = kb;
+        if constexpr (SHIFT) {  // the bin this one is without the integer CFO (|sh| <= 16 < N)
+            int32_t ks = static_cast<int32_t>(kb) - sh;
+            ks += ks < 0 ? static_cast<int32_t>(N) : ks >= static_cast<int32_t>(N) ? -static_cast<int32_t>(N) : 0;
+            k = static_cast<uint32_t>(ks);
+        }
         const uint32_t h = (k < N / 2 ? k : N - 1 - k) >> 5;  // 32-bin half-band, 0 at the centre
         const uint32_t band = h < 1 ? 0u : h < 2 ? 1u : h < 4 ? 2u : h < 8 ? 3u : h < 12 ? 4u : h < 16 ? 5u : SYNC_BANDS;
-        const double v = static_cast<double>(cnorm(S[k]));
+        const double v = static_cast<double>(cnorm(S[kb]));
 #pragma unroll
         for (uint32_t i = 0; i < SYNC_BANDS; ++i) p[i] += band == i ? v : 0.0;
     }
@@ -126,9 +142,6 @@ __device__ uint32_t sync_beta_decide(const sync_args& A, const float* band) {
     return b_est;
 }
 
-// ===================================================================== fine peak
-constexpr uint32_t SYNC_FINE_THREADS = 512;  // 8 waves: the FFT passes' butterflies 2 per thread
-
 // fractional CFO of a report: metric-weighted antenna mean of sync_post_kernel's terms, in antenna order
 __device__ __forceinline__ float sync_cfo_frac(const sync_args& A, const sync_res* rp, uint32_t rep) {
     float cfo_w = 0.f, msum = 0.f;
@@ -140,6 +153,73 @@ __device__ __forceinline__ float sync_cfo_frac(const sync_args& A, const sync_re
     }
     return cfo_w / msum;
 }
+
+// ===================================================================== integer CFO at the coarse peak
+// The project's own estimator (the reference leaves it unimplemented,
+// coarse_peak_f_domain.cpp:195-199), launched only with the search on, after sync_beta_kernel: the samples
+// sync_beta_kernel transforms, each multiplied by its pattern's cover-sequence sign (the STF periodic again,
+// its spectrum on the 4-subcarrier comb) and by the fractional-CFO correction the fine search applies, their
+// N-point transform, and per candidate k the power on the STF cells of the packet's b shifted by 4 k bins:
+// the comb bins 4 (i + k), 0 < |i| <= 7 b. One pass over the N / 4 comb bins, every candidate's sum in
+// registers. A candidate whose cells would reach N / 2 is not searched. Scores leave as floats, -1 for the
+// columns outside the range or not searched; sync_icfo_decide sums them in antenna order.
+// Six waves per SIMD asked for: the compiler's own choice is 85 VGPRs and five, with the budget 78, no spills.
+template <int LR, int MR, int HLR, bool CT>
+__global__ void __launch_bounds__(SYNC_THREADS) __attribute__((amdgpu_waves_per_eu(6))) sync_icfo_kernel(sync_args A, sync_beta_args B) {
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    static_assert(3 * (SYNC_THREADS / 64) * sizeof(double) <= 12 * sizeof(float2), "block_sum3's area: the 12 slots ahead of xb");
+    double* red = reinterpret_cast<double*>(smem);  // [12]: 3 sums x 4 waves (block_sum3)
+    const uint32_t N = B.plan.N;
+    float2* xb = smem + 12;
+    float2* yb = xb + N;
+    const uint32_t rep = blockIdx.x / A.n_ant, a = blockIdx.x % A.n_ant, w = rep / A.max_reports;
+    const sync_res* rp = A.res + rep;
+    if (!rp->found) return;  // uniform: the whole workgroup leaves
+    const float2* x = A.iq + w * A.win_stride + a * A.ant_stride;
+    resample_direct<LR, MR, HLR, CT>(A, x, static_cast<int64_t>(rp->coarse_local) + B.cp, N, [&](uint32_t i, float2 v) { xb[i] = v; });
+    __syncthreads();
+    const double cfo_frac = static_cast<double>(sync_cfo_frac(A, rp, rep));
+    // cover sequence and fractional CFO in a pass of their own: inside the polyphase blocks the phasors'
+    // doubles cost 18 VGPRs and a wave per SIMD
+    for (uint32_t i = threadIdx.x; i < N; i += blockDim.x)
+        xb[i] = cscale(cmul(xb[i], phasor(cfo_frac * static_cast<double>(i))), B.cover[i / A.pattern]);
+    __syncthreads();
+    const float2* S = fft_any<-1>(xb, yb, B.tw, B.plan);
+    // the packet's b: the class b, or the beta decision of this report (every thread the same sums)
+    const uint32_t b = A.beta_on ? sync_beta_decide(A, A.band + size_t(rep) * 8 * SYNC_BANDS) : A.b;
+    const int32_t h = 7 * static_cast<int32_t>(b), nc = static_cast<int32_t>(N / 4);  // cells 4 i, 0 < |i| <= h
+    double p[SYNC_ICFO_COLS] = {};
+    for (int32_t c = threadIdx.x; c < nc; c += blockDim.x) {
+        const int32_t cs = c < nc / 2 ? c : c - nc;  // comb index of bin 4 c, centred
+        const double v = static_cast<double>(cnorm(S[4 * c]));
+#pragma unroll
+        for (int32_t j = 0; j < static_cast<int32_t>(SYNC_ICFO_COLS); ++j) {
+            const int32_t i = cs - (j - static_cast<int32_t>(SYNC_ICFO_MAX));
+            p[j] += i != 0 && i >= -h && i <= h ? v : 0.0;
+        }
+    }
+    block_sum3(p[0], p[1], p[2], red);
+    block_sum3(p[3], p[4], p[5], red);
+    block_sum3(p[6], p[7], p[8], red);
+    if (threadIdx.x == 0) {
+        float* o = A.icfo + (size_t(rep) * 8 + a) * SYNC_ICFO_COLS;
+#pragma unroll
+        for (int32_t j = 0; j < static_cast<int32_t>(SYNC_ICFO_COLS); ++j) {
+            const int32_t ak = abs(j - static_cast<int32_t>(SYNC_ICFO_MAX));
+            o[j] = ak <= static_cast<int32_t>(A.icfo_range) && 2 * (h + ak) < nc ? static_cast<float>(p[j]) : -1.f;
+        }
+    }
+}
+
+// The decision of one report (sync_icfo_k, kernels.hpp) as its correction in radians per sample of the class
+// rate, the sign of cfo_frac: -k 4 2 pi / N, +0 for k = 0
+__device__ float sync_icfo_decide(const sync_args& A, uint32_t rep) {
+    const int32_t k = sync_icfo_k(A.icfo + size_t(rep) * 8 * SYNC_ICFO_COLS, A.n_ant);
+    return k == 0 ? 0.f : static_cast<float>(static_cast<double>(-k) * 8.0 * 3.14159265358979323846 / static_cast<double>(A.icfo_N));
+}
+
+// ===================================================================== fine peak
+constexpr uint32_t SYNC_FINE_THREADS = 512;  // 8 waves: the FFT passes' butterflies 2 per thread
 
 // The fine search of one workgroup (crosscorrelator.cpp:122-249), two forms:
 //  ALL = false  one workgroup per report: the antenna with the largest coarse-peak metric against every
@@ -223,7 +303,12 @@ __device__ __forceinline__ void sync_fine_body(const sync_args& A) {
             if (rp->coarse_metric[a] > rp->coarse_metric[best]) best = a;
         cfo_frac = rp->cfo_frac;
     }
-    const float cfo_hw = (cfo_frac + rp->cfo_int) * static_cast<float>(A.Mtx) / static_cast<float>(A.Ltx);
+    // integer CFO search on (kernel argument, uniform): the decision on sync_icfo_kernel's scores, every thread
+    // the same sums in the same order; off: the report's 0
+    const float cfo_int = A.icfo_range ? sync_icfo_decide(A, rep) : rp->cfo_int;
+    if constexpr (!ALL)
+        if (A.icfo_range && threadIdx.x == 0) rp->cfo_int = cfo_int;
+    const float cfo_hw = (cfo_frac + cfo_int) * static_cast<float>(A.Mtx) / static_cast<float>(A.Ltx);
     const int64_t base = rp->coarse_64 - static_cast<int64_t>(A.xc_l);
     const uint32_t stage_len = A.xc_len - 1 + A.tmpl_len;
     const float2* x = A.iq + w * A.win_stride + best * A.ant_stride;
@@ -354,6 +439,7 @@ __global__ void __launch_bounds__(SYNC_COMBINE_THREADS) sync_fine_combine_kernel
     if (!rp->found) return;
     rp->cfo_frac = sync_cfo_frac(A, rp, rep);
     if (A.beta_on) rp->b = sync_beta_decide(A, A.band + size_t(rep) * 8 * SYNC_BANDS);
+    if (A.icfo_range) rp->cfo_int = sync_icfo_decide(A, rep);
     float ms[4] = {0.f, 0.f, 0.f, 0.f}, wi[4] = {0.f, 0.f, 0.f, 0.f};
     for (uint32_t a = 0; a < A.n_ant; ++a) {
         if (!(rp->coarse_metric[a] > 0.f)) continue;
@@ -416,9 +502,27 @@ hipError_t launch_sync_post(const sync_args& a, uint32_t n, hipStream_t st) {
 hipError_t launch_sync_beta(const sync_args& a, const sync_beta_args& ba, uint32_t n, hipStream_t st) {
     const dim3 g(n * a.max_reports * a.n_ant);
     const size_t lds = (12 + 2 * size_t(ba.plan.N)) * sizeof(float2);
-    if (lds > LDS_BYTES || ba.cp + ba.plan.N != a.stf_len) return hipErrorInvalidValue;
+    if (lds > LDS_BYTES || ba.cp + ba.plan.N != a.stf_len || (ba.shift && (!a.icfo || !a.icfo_range))) return hipErrorInvalidValue;
     sync_dispatch<true>(a, [&](auto l, auto m, auto h, auto ct) {  // compiled-in 9/10 taps, as sync_post_kernel
-        hipLaunchKernelGGL((sync_beta_kernel<decltype(l)::value, decltype(m)::value, decltype(h)::value, decltype(ct)::value>), g,
+        constexpr int LR = decltype(l)::value, MR = decltype(m)::value, HLR = decltype(h)::value;
+        constexpr bool CT = decltype(ct)::value;
+        if (ba.shift)
+            hipLaunchKernelGGL((sync_beta_kernel<LR, MR, HLR, CT, true>), g, dim3(SYNC_THREADS), lds, st, a, ba);
+        else
+            hipLaunchKernelGGL((sync_beta_kernel<LR, MR, HLR, CT, false>), g, dim3(SYNC_THREADS), lds, st, a, ba);
+    });
+    return hipGetLastError();
+}
+
+// sync_beta_kernel's grid, LDS and class dispatch
+hipError_t launch_sync_icfo(const sync_args& a, const sync_beta_args& ba, uint32_t n, hipStream_t st) {
+    const dim3 g(n * a.max_reports * a.n_ant);
+    const size_t lds = (12 + 2 * size_t(ba.plan.N)) * sizeof(float2);
+    if (lds > LDS_BYTES || ba.cp + ba.plan.N != a.stf_len || ba.plan.N != 4 * a.pattern || a.icfo_N != ba.plan.N ||
+        a.icfo_range > SYNC_ICFO_MAX || !a.icfo)
+        return hipErrorInvalidValue;
+    sync_dispatch<true>(a, [&](auto l, auto m, auto h, auto ct) {
+        hipLaunchKernelGGL((sync_icfo_kernel<decltype(l)::value, decltype(m)::value, decltype(h)::value, decltype(ct)::value>), g,
                            dim3(SYNC_THREADS), lds, st, a, ba);
     });
     return hipGetLastError();

@@ -237,6 +237,7 @@ EXPORTS = ["dnrp_ctx_create", "dnrp_ctx_destroy", "dnrp_add_network_id", "dnrp_g
            "dnrp_pcc_encode_batch", "dnrp_query_table", "dnrp_ctx_set_rx_mode", "dnrp_ctx_set_tx_windowing",
            "dnrp_tx_window", "dnrp_ctx_set_sync_beta_search", "dnrp_ctx_get_sync_beta_search",
            "dnrp_ctx_set_sync_fine_all_antennas", "dnrp_ctx_get_sync_fine_all_antennas", "dnrp_rx_sync_fine_peaks",
+           "dnrp_ctx_set_sync_icfo_search", "dnrp_ctx_get_sync_icfo_search", "dnrp_rx_sync_icfo_scores",
            "dnrp_tx_last_form", "dnrp_tx_form_for", "dnrp_ctx_set_rx_sto_tracking", "dnrp_ctx_get_rx_sto_tracking",
            "dnrp_rx_sto_track", "dnrp_ctx_set_rx_mimo_report", "dnrp_ctx_get_rx_mimo_report", "dnrp_rx_mimo_detail",
            "dnrp_ctx_set_rx_cfo_tracking", "dnrp_ctx_get_rx_cfo_tracking", "dnrp_rx_cfo_track"]
@@ -276,6 +277,9 @@ def lib():
         L.dnrp_ctx_set_sync_fine_all_antennas.argtypes = [P, C.c_uint32]
         L.dnrp_ctx_get_sync_fine_all_antennas.argtypes = [P, C.POINTER(C.c_uint32)]
         L.dnrp_rx_sync_fine_peaks.argtypes = [P, C.c_uint32, P, P, P]
+        L.dnrp_ctx_set_sync_icfo_search.argtypes = [P, C.c_uint32]
+        L.dnrp_ctx_get_sync_icfo_search.argtypes = [P, C.POINTER(C.c_uint32)]
+        L.dnrp_rx_sync_icfo_scores.argtypes = [P, C.c_uint32, P, P, P]
         L.dnrp_ctx_set_rx_sto_tracking.argtypes = [P, C.c_uint32, C.c_float]
         L.dnrp_ctx_set_rx_cfo_tracking.argtypes = [P, C.c_uint32, C.c_float]
         L.dnrp_ctx_get_rx_cfo_tracking.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
@@ -372,6 +376,12 @@ def query_table(name, *args):
     _chk(min(0, lib().dnrp_query_table(str(name).encode(), ap, len(a), C.c_void_p(out.ctypes.data), n)),
          "dnrp_query_table")
     return out[:n]
+
+
+def sync_icfo_cells(N, b, k):
+    """Host-only: the bins, mod N, that candidate k of the integer CFO search sums for a packet of b in an
+    N-point transform (dnrp_query_table "sync_icfo_cells"); empty for a candidate that is not searched."""
+    return query_table("sync_icfo_cells", N, b, int(k) & 0xFFFFFFFF).astype(np.int64)
 
 
 def pcc_cells(b, N_TS):
@@ -542,6 +552,28 @@ class Phy:
         on = C.c_uint32()
         _chk(lib().dnrp_ctx_get_sync_fine_all_antennas(self._ctx, C.byref(on)), "dnrp_ctx_get_sync_fine_all_antennas")
         return bool(on.value)
+
+    def set_sync_icfo_search(self, search_range):
+        """dnrp_ctx_set_sync_icfo_search: every later rx_sync_batch / rx_sync_stream searches the integer CFO
+        k in [-search_range, search_range] (multiples of 4 subcarriers) at the coarse peak and reports
+        cfo_integer_rad = -k 8 pi / N; 0 (the default) = off, the synchronisation as it is without the search."""
+        _chk(lib().dnrp_ctx_set_sync_icfo_search(self._ctx, int(search_range)), "dnrp_ctx_set_sync_icfo_search")
+
+    def sync_icfo_search(self):
+        """dnrp_ctx_get_sync_icfo_search: the range, 0 = off"""
+        r = C.c_uint32()
+        _chk(lib().dnrp_ctx_get_sync_icfo_search(self._ctx, C.byref(r)), "dnrp_ctx_get_sync_icfo_search")
+        return int(r.value)
+
+    def sync_icfo_scores(self, n_reports, stream=None):
+        """dnrp_rx_sync_icfo_scores: (score float32 [n_reports, 8, 9] = (report slot of the latest rx_sync_batch,
+        antenna, candidate k + 4), k int32 [n_reports]); -1 where a candidate is outside the range or not
+        searched. n_reports = n * max_reports of that call, which ran with set_sync_icfo_search(1..4)."""
+        score = np.zeros((int(n_reports), 8, 9), np.float32)
+        k = np.zeros(int(n_reports), np.int32)
+        _chk(lib().dnrp_rx_sync_icfo_scores(self._ctx, int(n_reports), C.c_void_p(score.ctypes.data),
+                                            C.c_void_p(k.ctypes.data), _stream_ptr(stream)), "dnrp_rx_sync_icfo_scores")
+        return score, k
 
     def sync_fine_peaks(self, n_reports, stream=None):
         """dnrp_rx_sync_fine_peaks: (metric float32, index uint32), each [n_reports, 8, 4] = (report slot of the

@@ -52,7 +52,8 @@ extern "C" {
 #define DNRP_EDEVICE (-5)     /* HIP runtime error */
 #define DNRP_ENETID (-6)      /* network ID not registered with dnrp_add_network_id */
 #define DNRP_ESTATE (-7)      /* dnrp_rx_pdc_batch without a preceding dnrp_rx_pcc_batch; dnrp_rx_sync_fine_peaks
-                                 without a preceding dnrp_rx_sync_batch that ran with the setting on;
+                                 or dnrp_rx_sync_icfo_scores without a preceding dnrp_rx_sync_batch that ran with
+                                 the setting on;
                                  dnrp_rx_mimo_detail without a preceding dnrp_rx_pdc_batch that ran with detail = 1 */
 
 typedef struct dnrp_ctx dnrp_ctx;
@@ -101,7 +102,8 @@ typedef struct {
 typedef struct {
     int64_t fine_peak_time;   /* hw-rate sample index of the packet start inside its window */
     float cfo_fractional_rad; /* per DECT-rate sample */
-    float cfo_integer_rad;
+    float cfo_integer_rad;    /* per DECT-rate sample, added to cfo_fractional_rad: 0, or -k 8 pi / N_b_DFT_os of
+                                 dnrp_ctx_set_sync_icfo_search */
     uint32_t u, b, N_eff_TX;
     uint32_t window;          /* window of iq_in holding the packet (the sync window it was found in:
                                  several packets of one window share it) */
@@ -285,7 +287,12 @@ int dnrp_rx_sync_batch(dnrp_ctx* ctx, const dnrp_sync_cfg* sc, uint32_t n, const
  *    class rate; the fine search takes the rows of the report's b (crosscorrelator.cpp:159).
  * dnrp_sync_cfg::b stays the class maximum whose sample rate the stream has; the candidates are the
  * values of b_idx2b <= it, and the search ends there (the reference's loop would test one b further and
- * stops in its asserts). cfo_integer_rad stays 0 (the reference's integer-CFO search is an #error).
+ * stops in its asserts). cfo_integer_rad is the business of dnrp_ctx_set_sync_icfo_search below: the decision
+ * here reads the uncorrected band powers and comes first, the integer CFO search uses the decided b, and a
+ * report whose integer CFO is k != 0 has its b decided again from the spectrum moved back by 4 k bins. With both
+ * searches on, the b of such a report is therefore not the reference's estimate_beta on the raw spectrum but that
+ * estimator on the spectrum with the integer CFO taken out (this project's divergence); for k = 0, and with the
+ * integer CFO search off, it is the reference's.
  *   on            0 (default): exactly the synchronisation without the option, b = dnrp_sync_cfg::b, the
  *                 same templates, no further launch. 1: on for every later dnrp_rx_sync_batch and
  *                 dnrp_rx_sync_stream of the context (no context rebuild); the templates of the other b
@@ -336,6 +343,40 @@ int dnrp_ctx_get_sync_beta_search(const dnrp_ctx* ctx, uint32_t* on, float* thre
 int dnrp_ctx_set_sync_fine_all_antennas(dnrp_ctx* ctx, uint32_t on);
 int dnrp_ctx_get_sync_fine_all_antennas(const dnrp_ctx* ctx, uint32_t* on);
 int dnrp_rx_sync_fine_peaks(dnrp_ctx* ctx, uint32_t n_reports, float* metric, uint32_t* index, void* stream);
+
+/*
+ * Integer CFO search at the coarse peak <- the build option
+ * RX_SYNC_PARAM_AUTOCORRELATOR_PEAK_FIND_INTEGER_CFO_SEARCH_RANGE_OR_ASSUME_ZERO
+ * (lib/include/dectnrp/phy/rx/sync/sync_param.hpp:245-252), whose estimator the reference leaves as
+ * `#error "integer CFO not implemented yet"` (lib/src/phy/rx/sync/coarse_peak_f_domain.cpp:195-199). The
+ * estimator is this project's own. cfo_fractional_rad is unambiguous within +-2 subcarriers
+ * only (the STF patterns are N/4 samples apart); an offset of (4 k + f) subcarriers leaves f there and k
+ * unseen, and the fine search then misses the peak and N_eff_TX. With the search on, for every searched
+ * antenna the N = 64 b os_min DECT-rate samples the beta search transforms (the STF's last N at the coarse
+ * peak) are multiplied by their patterns' cover-sequence signs and by exp(j cfo_fractional_rad i), transformed,
+ * and candidate k scores the power on the bins 4 (i + k) mod N, 0 < |i| <= N_b_OCC(b') / 8, b' the report's b
+ * (the decided b with the beta search on). A candidate with 4 (N_b_OCC(b') / 8 + |k|) >= N / 2 is not
+ * searched. The scores are summed over the antennas in antenna order in float; the candidates are visited
+ * 0, -1, +1, -2, ... and a later one wins only if strictly greater. Then
+ *   cfo_integer_rad = (float)(-k 4 2 pi / N)   (+0 for k = 0),
+ * a correction with the sign of cfo_fractional_rad, the fine search pre-corrects with the sum of both, and
+ * dnrp_rx_pcc_batch mixes with the sum as before.
+ *   range  0 (default): exactly the synchronisation without the option: no further launch, cfo_integer_rad = 0,
+ *          byte-identical reports. 1..4: k in [-range, range] for every later dnrp_rx_sync_batch and
+ *          dnrp_rx_sync_stream of the context (no context rebuild).
+ * DNRP_EINVAL for a NULL context or range > 4. The getter's output may be NULL.
+ *
+ * dnrp_rx_sync_icfo_scores: the score table and the decided k of the context's latest dnrp_rx_sync_batch, which
+ * must have run with the search on. score is a host array [n_reports][8][9] ordered (report slot in `res`
+ * order, antenna, candidate k + 4), k a host array [n_reports]; n_reports must equal that call's
+ * n * max_reports. -1 in the columns outside the range or not searched, in the rows of antennas >=
+ * N_ant_limited and of slots not `found` (their k is 0). Synchronises `stream` before it returns. Not offered
+ * for dnrp_rx_sync_stream (DNRP_ESTATE after it). DNRP_ESTATE if the latest sync call ran with the search off
+ * or there was none; DNRP_EINVAL for a NULL pointer or another n_reports.
+ */
+int dnrp_ctx_set_sync_icfo_search(dnrp_ctx* ctx, uint32_t range);
+int dnrp_ctx_get_sync_icfo_search(const dnrp_ctx* ctx, uint32_t* range);
+int dnrp_rx_sync_icfo_scores(dnrp_ctx* ctx, uint32_t n_reports, float* score, int32_t* k, void* stream);
 
 /*
  * RX phase 1: synchronised PCC demodulation of n packets. Each packet is processed with the
