@@ -507,9 +507,14 @@ double oracle_loopback_timed(const uint32_t* cfg, const uint32_t* psdef, uint32_
 //   coarse_local, coarse_64, cfo_frac, u, b, N_eff_TX, fine_local, fine_64, coarse_metric[8],
 //   rms[8], xc_metric[4], xc_idx[4]
 static constexpr int SYNC_NF = 38;
-int oracle_sync(const uint32_t* scfg, const float* iq, uint32_t S_win, uint32_t max_reports, int use_float,
-                double* out) {
+// trace [SYNC_TRACE_NF] doubles (may be null): ignored_steps, evaluated_steps, false_alarms, stf_before_chunk,
+//   fine_outside, resampler_outside, closest_metric, 0, rms_min_rej[8], rms_max_rej[8], front_back_rej[8],
+//   invalid_at_peak[8] (oracle_dsp.hpp sync_trace_t); mutant: SYNC_MUTANT_* bits
+static constexpr int SYNC_TRACE_NF = 40;
+int oracle_sync_trace(const uint32_t* scfg, const float* iq, uint32_t S_win, uint32_t max_reports, int use_float,
+                      uint32_t mutant, double* out, double* trace) {
     try {
+        sync_trace_t tr;
         sync_cfg_t c;
         c.u = scfg[0];
         c.b = scfg[1];
@@ -519,8 +524,20 @@ int oracle_sync(const uint32_t* scfg, const float* iq, uint32_t S_win, uint32_t 
         c.N_ant = scfg[5];
         c.N_ant_limited = scfg[6];
         c.chunk_len = scfg[7];
-        const auto r = use_float ? sync_search<float>(c, iq, S_win, max_reports)
-                                 : sync_search<double>(c, iq, S_win, max_reports);
+        const auto r = use_float ? sync_search<float>(c, iq, S_win, max_reports, &tr, mutant)
+                                 : sync_search<double>(c, iq, S_win, max_reports, &tr, mutant);
+        if (trace) {
+            const double v[8] = {double(tr.ignored_steps), double(tr.evaluated_steps), double(tr.false_alarms),
+                                 double(tr.stf_before_chunk), double(tr.fine_outside), double(tr.resampler_outside),
+                                 tr.closest_metric, 0.0};
+            for (int k = 0; k < 8; ++k) {
+                trace[k] = v[k];
+                trace[8 + k] = tr.rms_min_rej[k];
+                trace[16 + k] = tr.rms_max_rej[k];
+                trace[24 + k] = tr.front_back_rej[k];
+                trace[32 + k] = tr.invalid_at_peak[k];
+            }
+        }
         for (size_t i = 0; i < r.size(); ++i) {
             const auto& o = r[i];
             double* d = out + i * SYNC_NF;
@@ -539,6 +556,11 @@ int oracle_sync(const uint32_t* scfg, const float* iq, uint32_t S_win, uint32_t 
         std::fprintf(stderr, "oracle_sync: %s\n", e.what());
         return -2;
     }
+}
+
+int oracle_sync(const uint32_t* scfg, const float* iq, uint32_t S_win, uint32_t max_reports, int use_float,
+                double* out) {
+    return oracle_sync_trace(scfg, iq, S_win, max_reports, use_float, 0, out, nullptr);
 }
 
 // out: geometry n_pattern, bos, stf_len, pattern, step, A, B, C, D, search_len, lb_len, xc_l,

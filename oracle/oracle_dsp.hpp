@@ -101,9 +101,24 @@ struct sync_out_t {  // sync_report_t (sync_report.hpp:29-98)
     float xc_metric[4];
     uint32_t xc_idx[4];
 };
+// Which branches a search took (tests/test_sync_edges_host.py): counts over the whole window.
+struct sync_trace_t {
+    uint32_t ignored_steps = 0;      // steps skipped by ignore_before (chunk head, skip_after_peak)
+    uint32_t evaluated_steps = 0;    // steps whose antennas were looked at
+    uint32_t rms_min_rej[8] = {}, rms_max_rej[8] = {}, front_back_rej[8] = {};  // per antenna, in detection order
+    uint32_t false_alarms = 0;       // detections with no valid coarse peak (nvalid == 0)
+    uint32_t stf_before_chunk = 0;   // coarse peaks whose STF starts before the chunk
+    uint32_t invalid_at_peak[8] = {};  // per antenna: reports that left it out of the coarse peak
+    uint32_t fine_outside = 0;       // fine-stage samples outside [0, S_win), over all reports
+    uint32_t resampler_outside = 0;  // window samples >= S_win under the taps of a resampler output the search read
+    double closest_metric = 1e30;    // min |metric - METRIC_MIN| / METRIC_MIN over evaluated steps that did not
+                                     // detect, antennas inside the RMS gates
+};
+enum : uint32_t { SYNC_MUTANT_ANT0_UNGATED = 1 };  // wrong-kernel model: antenna 0 passes the RMS gates
 sync_geom_t sync_geometry(const sync_cfg_t& c);
 std::vector<cd> stf_template(const sync_cfg_t& c, uint32_t N_eff_TX);
 template <typename R>
-std::vector<sync_out_t> sync_search(const sync_cfg_t& c, const float* iq, uint32_t S_win, uint32_t max_reports);
+std::vector<sync_out_t> sync_search(const sync_cfg_t& c, const float* iq, uint32_t S_win, uint32_t max_reports,
+                                    sync_trace_t* trace = nullptr, uint32_t mutant = 0);
 
 }  // namespace orc

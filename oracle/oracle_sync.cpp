@@ -180,11 +180,15 @@ std::vector<cd> stf_template(const sync_cfg_t& c, uint32_t N_eff_TX) {
 }
 
 template <typename R>
-std::vector<sync_out_t> sync_search(const sync_cfg_t& c, const float* iq, uint32_t S_win, uint32_t max_reports) {
+std::vector<sync_out_t> sync_search(const sync_cfg_t& c, const float* iq, uint32_t S_win, uint32_t max_reports,
+                                    sync_trace_t* trace, uint32_t mutant) {
     using C = std::complex<R>;
     const sync_geom_t g = sync_geometry(c);
     const uint32_t NA = c.N_ant_limited;
     std::vector<sync_out_t> res;
+    sync_trace_t tr_local;
+    sync_trace_t& tr = trace ? *trace : tr_local;
+    uint32_t lb_used = 0;  // one past the last resampler output the search read
 
     // ---- sync resampler output for the whole chunk (zero history at the chunk start)
     resampler_t rs;
@@ -277,16 +281,39 @@ std::vector<sync_out_t> sync_search(const sync_cfg_t& c, const float* iq, uint32
             resum_cnt = 0;
         }
         r += g.step;
-        if (ignore_before > r) continue;
+        lb_used = std::max(lb_used, r);
+        if (ignore_before > r) {
+            ++tr.ignored_steps;
+            continue;
+        }
+        ++tr.evaluated_steps;
         int det = -1;
         R det_rms = 0, det_metric = 0;
         for (uint32_t a = 0; a < NA && det < 0; ++a) {
             const R power = dpow[a].sum;
             const R rms = std::sqrt(power / static_cast<R>(g.stf_len));
-            if (rms < static_cast<R>(g.rms_min) || static_cast<R>(prm::RMS_MAX) < rms) continue;
+            const bool ungated = (mutant & SYNC_MUTANT_ANT0_UNGATED) && a == 0;
+            if (!ungated && rms < static_cast<R>(g.rms_min)) {
+                ++tr.rms_min_rej[a];
+                continue;
+            }
+            if (!ungated && static_cast<R>(prm::RMS_MAX) < rms) {
+                ++tr.rms_max_rej[a];
+                continue;
+            }
+            if (trace) {  // how close this antenna's metric is to the threshold, whatever the later gates say
+                const R qt = prefactor * std::abs(dcorr[a].sum) / power;
+                const double mt = static_cast<double>(qt * qt);
+                if (!(static_cast<double>(prm::METRIC_MIN) < mt) && mt == mt)
+                    tr.closest_metric = std::min(tr.closest_metric, std::abs(mt - static_cast<double>(prm::METRIC_MIN)) /
+                                                                        static_cast<double>(prm::METRIC_MIN));
+            }
             const R rms_back = std::sqrt(dpow[a].sum_back(prm::RMS_BACK_STEPS));
             const R rms_front = std::sqrt(dpow[a].sum_front(prm::RMS_FRONT_STEPS));
-            if (rms_back * static_cast<R>(prm::RMS_FRONT_TO_BACK) >= rms_front) continue;
+            if (rms_back * static_cast<R>(prm::RMS_FRONT_TO_BACK) >= rms_front) {
+                ++tr.front_back_rej[a];
+                continue;
+            }
             const R q = prefactor * std::abs(dcorr[a].sum) / power;
             const R metric = q * q;
             static_assert(prm::STREAK == 1 && prm::STREAK_GAIN == 0.0f, "single-step streak");
@@ -307,6 +334,7 @@ std::vector<sync_out_t> sync_search(const sync_cfg_t& c, const float* iq, uint32
         o.det_time_jb = r - prm::JUMP_BACK_PATTERNS * g.pattern;
         o.u = c.u;
         const uint32_t r0 = o.det_time_jb, r_max = r0 + g.D;
+        lb_used = std::max(lb_used, r_max);
         set_initial_movsums(r0 - g.stf_len);
         std::vector<R> pk_metric(NA, 0);
         std::vector<uint32_t> pk_idx(NA, 0);
@@ -350,12 +378,21 @@ std::vector<sync_out_t> sync_search(const sync_cfg_t& c, const float* iq, uint32
             wsum += m * static_cast<float>(pk_idx[a]);
             ++nvalid;
         }
-        if (nvalid == 0) continue;  // false alarm: detection continues after this step
+        if (nvalid == 0) {  // false alarm: detection continues after this step
+            ++tr.false_alarms;
+            continue;
+        }
         float msum = 0.f;  // coarse_peak_array.get_sum()
         for (uint32_t a = 0; a < NA; ++a) msum += o.coarse_metric[a];
         const uint32_t wpk = static_cast<uint32_t>(std::round(wsum / msum));
-        if (wpk < g.stf_len - 1) continue;  // STF before the chunk start (asserted in the reference)
+        if (wpk < g.stf_len - 1) {  // STF before the chunk start (asserted in the reference)
+            ++tr.stf_before_chunk;
+            continue;
+        }
         const uint32_t cpl = wpk - (g.stf_len - 1);
+        lb_used = std::max(lb_used, cpl + g.stf_len + g.pattern);  // set_initial_movsums(cpl)
+        for (uint32_t a = 0; a < NA; ++a)
+            if (!(o.coarse_metric[a] > 0.0f)) ++tr.invalid_at_peak[a];
         o.coarse_local = cpl;
         // post_processing_at_coarse_peak (autocorrelator_peak.cpp:366-394)
         set_initial_movsums(cpl);
@@ -390,7 +427,9 @@ std::vector<sync_out_t> sync_search(const sync_cfg_t& c, const float* iq, uint32
         const float* s = iq + 2ull * best * S_win;
         for (uint32_t i = 0; i < stage_len; ++i) {
             const int64_t q = base + i;
-            const cd v = (q >= 0 && q < static_cast<int64_t>(S_win)) ? cd(s[2 * q], s[2 * q + 1]) : cd(0, 0);
+            const bool inside = q >= 0 && q < static_cast<int64_t>(S_win);
+            if (!inside) ++tr.fine_outside;
+            const cd v = inside ? cd(s[2 * q], s[2 * q + 1]) : cd(0, 0);
             const double ph = cfo_hw * static_cast<double>(i);
             stage[i] = v * cd(std::cos(ph), std::sin(ph));
         }
@@ -421,10 +460,22 @@ std::vector<sync_out_t> sync_search(const sync_cfg_t& c, const float* iq, uint32
         o.found = 1;
         res.push_back(o);
     }
+    // window samples past S_win that lie under the taps of an output the search read (read as zeros above)
+    {
+        const uint32_t used = std::min(lb_used, g.lb_len);
+        int64_t last = -1;
+        if (used) {
+            if (rs.L == 1 && rs.M == 1) last = static_cast<int64_t>(used) - 1;
+            else last = static_cast<int64_t>((rs.delay + static_cast<uint64_t>(used - 1) * rs.M) / rs.L);
+        }
+        if (last >= static_cast<int64_t>(S_win)) tr.resampler_outside = static_cast<uint32_t>(last + 1 - S_win);
+    }
     return res;
 }
 
-template std::vector<sync_out_t> sync_search<double>(const sync_cfg_t&, const float*, uint32_t, uint32_t);
-template std::vector<sync_out_t> sync_search<float>(const sync_cfg_t&, const float*, uint32_t, uint32_t);
+template std::vector<sync_out_t> sync_search<double>(const sync_cfg_t&, const float*, uint32_t, uint32_t, sync_trace_t*,
+                                                     uint32_t);
+template std::vector<sync_out_t> sync_search<float>(const sync_cfg_t&, const float*, uint32_t, uint32_t, sync_trace_t*,
+                                                    uint32_t);
 
 }  // namespace orc

@@ -66,6 +66,7 @@ def lib():
                                      C.c_uint32]
         L.oracle_special.argtypes = [C.c_float, F32P]
         L.oracle_sync.argtypes = [U32P, F32P, C.c_uint32, C.c_uint32, C.c_int, F64P]
+        L.oracle_sync_trace.argtypes = [U32P, F32P, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, F64P, F64P]
         L.oracle_sync_geometry.argtypes = [U32P, U32P, C.POINTER(C.c_float)]
         L.oracle_stf_template.argtypes = [U32P, C.c_uint32, F32P]
         L.oracle_query_param.argtypes = [C.c_char_p, C.POINTER(C.c_double)]
@@ -311,13 +312,33 @@ def stf_template(scfg, n_eff_tx):
     return out.view(np.complex64).copy()
 
 
+SYNC_MUTANT_ANT0_UNGATED = 1  # oracle_dsp.hpp: antenna 0 passes the RMS gates (a wrong-kernel model)
+SYNC_TRACE_SCALARS = ["ignored_steps", "evaluated_steps", "false_alarms", "stf_before_chunk", "fine_outside",
+                      "resampler_outside", "closest_metric"]
+SYNC_TRACE_ARRAYS = ["rms_min_rej", "rms_max_rej", "front_back_rej", "invalid_at_peak"]
+
+
 def sync(scfg, iq, max_reports=4, use_float=False):
     """iq: complex64 [N_ant_limited, S_win] window (chunk starting at iq[:, 0]). Returns a list of dicts."""
+    return sync_trace(scfg, iq, max_reports, use_float)[0]
+
+
+def sync_trace(scfg, iq, max_reports=4, use_float=False, mutant=0):
+    """sync() and the branches the search took (oracle_dsp.hpp sync_trace_t): (reports, trace dict). The per-antenna
+    counts are int arrays of 8; closest_metric is 1e30 where no evaluated step came below the threshold."""
     iq = np.ascontiguousarray(iq, dtype=np.complex64)
     out = np.zeros((max_reports, 38), np.float64)
-    n = lib().oracle_sync(np.asarray(scfg, np.uint32), iq.view(np.float32).reshape(-1), iq.shape[1], max_reports,
-                          int(use_float), out)
+    tr = np.zeros(40, np.float64)
+    n = lib().oracle_sync_trace(np.asarray(scfg, np.uint32), iq.view(np.float32).reshape(-1), iq.shape[1], max_reports,
+                                int(use_float), int(mutant), out, tr)
     assert n >= 0, n
+    trace = {k: (float(tr[j]) if k == "closest_metric" else int(tr[j])) for j, k in enumerate(SYNC_TRACE_SCALARS)}
+    for j, k in enumerate(SYNC_TRACE_ARRAYS):
+        trace[k] = tr[8 + 8 * j:16 + 8 * j].astype(np.int64)
+    return _sync_dicts(out, n), trace
+
+
+def _sync_dicts(out, n):
     res = []
     for i in range(n):
         d = {k: out[i, j] for j, k in enumerate(SYNC_KEYS)}
