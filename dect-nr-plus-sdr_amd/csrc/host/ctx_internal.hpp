@@ -287,6 +287,16 @@ struct sync_tables {  // per (u, b) of the searched STF: sync_chunk_t / crosscor
     dev::fft_plan beta_plan{};
 };
 
+// rx.cpp: the azimuth grid of an angle-of-arrival setting and its steering table, for the device scan
+// (dnrp_ctx_set_rx_aoa uploads it) and the host twin (dnrp_aoa_estimate) alike
+struct aoa_grid {
+    uint32_t n_grid = 0, cyclic = 0;
+    double az0 = 0.0, step = 0.0;  // az_g = az0 + g step
+};
+bool aoa_cfg_ok(const dnrp_aoa_cfg* cfg);
+aoa_grid aoa_grid_of(const dnrp_aoa_cfg& cfg);
+std::vector<double2> aoa_steering(const dnrp_aoa_cfg& cfg, const aoa_grid& g, uint32_t N_RX);  // [n_grid][N_RX]
+
 // tables.cpp: the tables of a configuration, built and uploaded at its first use (nullptr: *err set)
 tx_tables* get_tx(dnrp_ctx* ctx, const dnrp_psdef& d, int* err);
 rx1_tables* get_rx1(dnrp_ctx* ctx, uint32_t u, uint32_t b, uint32_t N_eff_TX, int* err);
@@ -356,6 +366,18 @@ struct dnrp_ctx {
     uint32_t mimo_metric = 0, mimo_all_w = 0, mimo_detail = 0;
     uint32_t mimo_rows_m = 0;
     dbuf mimo_rows;
+    // angle-of-arrival report (dnrp_ctx_set_rx_aoa): the setting with its steering table, null = off; every setter
+    // call makes a new object, so the launches of a PDC call in flight keep the table they took (aoa_used: the
+    // latest PDC call's, alive until the next one replaces it). aoa_rows: one dnrp_aoa_report per request of the
+    // latest PDC call that ran rx_aoa_kernel, aoa_rows_m: that call's m, else 0 (dnrp_rx_aoa)
+    struct aoa_setting {
+        dnrp_aoa_cfg cfg{};
+        dnrp::host::aoa_grid grid{};
+        dbuf steer;  // [n_grid][N_RX] double2
+    };
+    std::shared_ptr<aoa_setting> aoa, aoa_used;
+    uint32_t aoa_rows_m = 0;
+    dbuf aoa_rows;
     pinned st_tx, st_rxin, st_seq, st_rep;
     // retained RX phase-1 state: per PCC-batch slot its (u, b, N_eff_TX) tables and symbol
     // capacity; Y is laid out with the batch-wide maxima rx_nsym_cap / rx_Nf_pad

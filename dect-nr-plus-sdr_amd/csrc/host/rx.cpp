@@ -1,4 +1,6 @@
 // dnrp_rx_pcc_batch / dnrp_rx_pdc_batch (include/dnrp.h): the launches of the two RX phases.
+#include <cstddef>
+
 #include "ctx_internal.hpp"
 
 using namespace dnrp;
@@ -200,11 +202,13 @@ enum class pdc_path {
 // sto_track: residual STO or CFO tracking is on (dnrp_ctx_set_rx_sto_tracking, dnrp_ctx_set_rx_cfo_tracking);
 // the fused receiver and the grouped Y path, the two measured-slower alternatives, do not take the per-symbol
 // tables and are never chosen then
+// aoa: the angle-of-arrival report is on (dnrp_ctx_set_rx_aoa); it reads the packet's DRS rows from Y, where the
+// fused receiver does not leave them
 pdc_path choose_pdc_path(const switches& sw, const rx1_tables* t, const rx2_tables* t2, const dev::rx_front_args& fa,
-                         const dev::rx_cells_args& ca, uint32_t ng, bool sto_track) {
+                         const dev::rx_cells_args& ca, uint32_t ng, bool sto_track, bool aoa) {
     // both fused forms: the compile-time-tap wave front end and an instantiated (N_RX, N_eff_TX) pair
     const bool wave = fa.stream && dev::rx_fft_wave_path(fa);
-    if (!sto_track && sw.rx_fused && t2->fused_ok && fa.zd && wave && dev::rx_fused_supported(fa.N_RX, t->N_eff_TX) &&
+    if (!sto_track && !aoa && sw.rx_fused && t2->fused_ok && fa.zd && wave && dev::rx_fused_supported(fa.N_RX, t->N_eff_TX) &&
         dev::rx_fused_lds(fa.N_RX) <= dev::LDS_BYTES)
         return pdc_path::fused;
     if ((sw.rx_epoch >= 2 || (sw.rx_epoch == 1 && fa.N_RX >= 4)) && t2->ep_ok && !t2->sm && wave &&
@@ -472,13 +476,37 @@ int pdc_mimo_detail(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, cons
     return DNRP_OK;
 }
 
+static_assert(sizeof(dev::rx_aoa_row) == sizeof(dnrp_aoa_report) && offsetof(dev::rx_aoa_row, n_cells) == offsetof(dnrp_aoa_report, n_cells) &&
+                  offsetof(dev::rx_aoa_row, az_rad) == offsetof(dnrp_aoa_report, az_rad) &&
+                  offsetof(dev::rx_aoa_row, lag_re) == offsetof(dnrp_aoa_report, lag_re) &&
+                  offsetof(dev::rx_aoa_row, reserved) == offsetof(dnrp_aoa_report, reserved),
+              "dnrp_aoa_report layout");
+
+// the angle-of-arrival report of a launch group under the setting s the PDC call read: every DRS row of the
+// packet is in Y behind any receiver but the fused one, which is not chosen then (the grouped Y path's auxiliary
+// stream has joined st by now)
+int pdc_aoa(dnrp_ctx* ctx, const rx_phase& p, const dnrp_ctx::aoa_setting& s, hipStream_t st) {
+    dev::rx_aoa_args a{};
+    a.V = drs_view(ctx, p);
+    a.steer = s.steer.as<double2>();
+    a.n_grid = s.grid.n_grid;
+    a.cyclic = s.grid.cyclic;
+    a.az0 = s.grid.az0;
+    a.step = s.grid.step;
+    a.rows = ctx->aoa_rows.as<dev::rx_aoa_row>();
+    ctx->tic("rx_aoa", st);
+    if (dev::launch_rx_aoa(a, p.n, st) != hipSuccess) return DNRP_EDEVICE;
+    ctx->toc("rx_aoa", st);
+    return DNRP_OK;
+}
+
 // one launch group of the PDC call: its receiver, then the MIMO report where the caller asked for reports (or,
-// with the detailed report on, for its rows)
+// with the detailed report on, for its rows), then the angle-of-arrival report where that setting is on
 int pdc_group(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const float* iq_in, bool mimo, const mimo_opts& mo,
-              hipStream_t st) {
+              const dnrp_ctx::aoa_setting* aoa, hipStream_t st) {
     auto fa = front_args(ctx, p.t, iq_in, p.sel, snr_from_front(ctx, p.t) ? p.plan : nullptr);
     const auto ca = cells_args(ctx, p);
-    const pdc_path path = choose_pdc_path(ctx->sw, p.t, t2, fa, ca, p.n, rx_tracking(ctx));
+    const pdc_path path = choose_pdc_path(ctx->sw, p.t, t2, fa, ca, p.n, rx_tracking(ctx), aoa != nullptr);
     if (rx_tracking(ctx)) {  // the PCC plan's ops are the PDC plan's ops up to pcc_max: the state continues there
         uint32_t d0 = 0;
         while (d0 < p.plan->n_dops && p.plan->dl_h[d0] <= p.t->pcc_max) ++d0;
@@ -495,8 +523,9 @@ int pdc_group(dnrp_ctx* ctx, const rx_phase& p, const rx2_tables* t2, const floa
         case pdc_path::grouped_y: err = pdc_grouped_y(ctx, p, t2, fa, st); break;
         case pdc_path::plain_y: err = pdc_plain_y(ctx, p, t2, fa, ca, st); break;
     }
-    if (err != DNRP_OK || !mimo) return err;
-    return mo.on() ? pdc_mimo_detail(ctx, p, t2, fa, mo, st) : pdc_mimo(ctx, p, t2, fa, st);
+    if (err == DNRP_OK && mimo) err = mo.on() ? pdc_mimo_detail(ctx, p, t2, fa, mo, st) : pdc_mimo(ctx, p, t2, fa, st);
+    if (err == DNRP_OK && aoa) err = pdc_aoa(ctx, p, *aoa, st);
+    return err;
 }
 
 // the PDC reports of the call: the SNR chain's PDC estimate and the MIMO report of every request
@@ -546,6 +575,42 @@ int track_rows(dnrp_ctx* ctx, bool on, bool copy, uint32_t n_slots, uint32_t n_s
 }
 
 }  // namespace
+
+// ---- the angle-of-arrival setting: validation, azimuth grid and steering table (dnrp.h dnrp_ctx_set_rx_aoa)
+namespace {
+constexpr double AOA_TWO_PI = 6.283185307179586476925, AOA_SPAN_TOL = 1e-5;
+}
+
+bool dnrp::host::aoa_cfg_ok(const dnrp_aoa_cfg* cfg) {
+    for (int r = 0; r < 8; ++r)
+        if (!std::isfinite(cfg->pos[r][0]) || !std::isfinite(cfg->pos[r][1])) return false;
+    if (!std::isfinite(cfg->az_min) || !std::isfinite(cfg->az_max)) return false;
+    const double span = static_cast<double>(cfg->az_max) - static_cast<double>(cfg->az_min);
+    return span > 0.0 && span <= AOA_TWO_PI + AOA_SPAN_TOL && cfg->n_grid >= 8 && cfg->n_grid <= dev::RX_AOA_MAX_GRID &&
+           cfg->reserved == 0;
+}
+
+aoa_grid dnrp::host::aoa_grid_of(const dnrp_aoa_cfg& cfg) {
+    const double span = static_cast<double>(cfg.az_max) - static_cast<double>(cfg.az_min);
+    aoa_grid g;
+    g.n_grid = cfg.n_grid;
+    g.cyclic = std::fabs(span - AOA_TWO_PI) <= AOA_SPAN_TOL ? 1u : 0u;
+    g.az0 = cfg.az_min;
+    g.step = g.cyclic ? AOA_TWO_PI / cfg.n_grid : span / (cfg.n_grid - 1);
+    return g;
+}
+
+std::vector<double2> dnrp::host::aoa_steering(const dnrp_aoa_cfg& cfg, const aoa_grid& g, uint32_t N_RX) {
+    std::vector<double2> s(size_t(g.n_grid) * N_RX);
+    for (uint32_t i = 0; i < g.n_grid; ++i) {
+        const double az = g.az0 + i * g.step, c = std::cos(az), sn = std::sin(az);
+        for (uint32_t r = 0; r < N_RX; ++r) {
+            const double ph = AOA_TWO_PI * (static_cast<double>(cfg.pos[r][0]) * c + static_cast<double>(cfg.pos[r][1]) * sn);
+            s[size_t(i) * N_RX + r] = make_double2(std::cos(ph), std::sin(ph));
+        }
+    }
+    return s;
+}
 
 extern "C" {
 
@@ -768,6 +833,11 @@ int dnrp_rx_pdc_batch(dnrp_ctx* ctx, uint32_t m, const dnrp_pdc_req* req, const 
     ctx->mimo_rows_m = 0;
     if (mimo && !ctx->mimo_out.ensure(size_t(ctx->cfg.max_batch) * 3 * sizeof(uint32_t))) return DNRP_ENOMEM;
     if (mimo && mo.on() && !ctx->mimo_rows.ensure(size_t(ctx->cfg.max_batch) * sizeof(dnrp_mimo_detail))) return DNRP_ENOMEM;
+    // the angle-of-arrival setting likewise: this call's launches keep the object they took here
+    ctx->aoa_rows_m = 0;
+    if (ctx->aoa_used != ctx->aoa) ctx->aoa_used = ctx->aoa;
+    const dnrp_ctx::aoa_setting* aoa = ctx->aoa_used.get();
+    if (aoa && !ctx->aoa_rows.ensure(size_t(ctx->cfg.max_batch) * sizeof(dnrp_aoa_report))) return DNRP_ENOMEM;
     uint32_t off = 0;
     size_t gi = 0;
     for (const auto& g : groups) {
@@ -778,10 +848,11 @@ int dnrp_rx_pdc_batch(dnrp_ctx* ctx, uint32_t m, const dnrp_pdc_req* req, const 
         off += ng;
         const rx_phase p{t, &t2->bplan, ng, gsel, true, t2->q.N_bps, t2->pdc_k.as<uint32_t>(), t2->pdc_sym.as<uint16_t>(),
                          pdc_llr, llr_stride, t2->sm};
-        err = pdc_group(ctx, p, t2, iq_in, mimo, mo, st);
+        err = pdc_group(ctx, p, t2, iq_in, mimo, mo, aoa, st);
         if (err != DNRP_OK) return err;
     }
     if (mo.detail) ctx->mimo_rows_m = m;
+    if (aoa) ctx->aoa_rows_m = m;
     return rep ? pdc_reports(ctx, m, req, rep, st) : DNRP_OK;
 }
 
@@ -808,6 +879,62 @@ int dnrp_rx_mimo_detail(dnrp_ctx* ctx, uint32_t m, dnrp_mimo_detail* out, void* 
     (void)hipSetDevice(ctx->cfg.device);
     HIPCHK(hipMemcpyAsync(out, ctx->mimo_rows.p, size_t(m) * sizeof(dnrp_mimo_detail), hipMemcpyDeviceToHost,
                           static_cast<hipStream_t>(stream)));
+    return DNRP_OK;
+}
+
+int dnrp_ctx_set_rx_aoa(dnrp_ctx* ctx, const dnrp_aoa_cfg* cfg) {
+    if (!ctx) return DNRP_EINVAL;
+    if (!cfg) {
+        ctx->aoa.reset();
+        return DNRP_OK;
+    }
+    if (ctx->cfg.N_TX_max < 2 || !aoa_cfg_ok(cfg)) return DNRP_EINVAL;
+    (void)hipSetDevice(ctx->cfg.device);
+    auto s = std::make_shared<dnrp_ctx::aoa_setting>();
+    s->cfg = *cfg;
+    s->grid = aoa_grid_of(*cfg);
+    if (!s->steer.upload(aoa_steering(*cfg, s->grid, ctx->cfg.N_TX_max))) return DNRP_ENOMEM;
+    ctx->aoa = std::move(s);
+    return DNRP_OK;
+}
+
+int dnrp_ctx_get_rx_aoa(const dnrp_ctx* ctx, uint32_t* on, dnrp_aoa_cfg* cfg) {
+    if (!ctx) return DNRP_EINVAL;
+    if (on) *on = ctx->aoa ? 1u : 0u;
+    if (cfg && ctx->aoa) *cfg = ctx->aoa->cfg;
+    return DNRP_OK;
+}
+
+int dnrp_rx_aoa(dnrp_ctx* ctx, uint32_t m, dnrp_aoa_report* out, void* stream) {
+    if (!ctx || !out || m == 0) return DNRP_EINVAL;
+    if (!ctx->aoa_rows_m) return DNRP_ESTATE;
+    if (m > ctx->aoa_rows_m) return DNRP_EINVAL;
+    (void)hipSetDevice(ctx->cfg.device);
+    HIPCHK(hipMemcpyAsync(out, ctx->aoa_rows.p, size_t(m) * sizeof(dnrp_aoa_report), hipMemcpyDeviceToHost,
+                          static_cast<hipStream_t>(stream)));
+    return DNRP_OK;
+}
+
+int dnrp_aoa_estimate(const dnrp_aoa_cfg* cfg, uint32_t N_RX, const float* R, dnrp_aoa_report* out, float* spectrum) {
+    if (!cfg || !R || !out || N_RX < 2 || N_RX > 8 || !aoa_cfg_ok(cfg)) return DNRP_EINVAL;
+    const aoa_grid g = aoa_grid_of(*cfg);
+    const std::vector<double2> steer = aoa_steering(*cfg, g, N_RX);
+    const double tr = dev::aoa_trace(R, N_RX);
+    std::vector<double> P(g.n_grid, 0.0);
+    uint32_t best = 0;
+    for (uint32_t i = 0; i < g.n_grid; ++i) {
+        if (tr > 0.0) P[i] = dev::aoa_quad(R, steer.data() + size_t(i) * N_RX, N_RX) / (static_cast<double>(N_RX) * tr);
+        if (P[i] > P[best]) best = i;
+        if (spectrum) spectrum[i] = static_cast<float>(P[i]);
+    }
+    dev::rx_aoa_row row{};
+    dev::aoa_finish(R, N_RX, P.data(), g.n_grid, g.cyclic, g.az0, g.step, tr, best, &row);
+    out->grid_idx = row.grid_idx;
+    out->az_rad = row.az_rad;
+    out->peak = row.peak;
+    out->lag_re = row.lag_re;
+    out->lag_im = row.lag_im;
+    out->reserved[0] = out->reserved[1] = 0;
     return DNRP_OK;
 }
 

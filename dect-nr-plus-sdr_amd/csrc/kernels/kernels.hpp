@@ -455,6 +455,82 @@ struct rx_mimo_detail_args {
 };
 hipError_t launch_rx_mimo_detail(const rx_mimo_detail_args& a, uint32_t n, hipStream_t st);
 
+// ---- angle-of-arrival report (dnrp_ctx_set_rx_aoa): rx_aoa_kernel in rx_drs.hip, one workgroup per
+// packet at the end of the PDC phase: the spatial covariance of the zero-forced DRS pilots of every op of the
+// PDC plan, then a Bartlett scan of it over the setting's azimuth grid
+constexpr uint32_t RX_AOA_MAX_GRID = 512, RX_AOA_NONE = 0xFFFFFFFFu;
+struct rx_aoa_row {  // dnrp_aoa_report, field for field (rx.cpp asserts the layout)
+    float R[8][8][2];
+    uint32_t n_cells, grid_idx;
+    float az_rad, peak, lag_re, lag_im;
+    uint32_t reserved[2];
+};
+struct rx_aoa_args {
+    rx_drs_view V;          // the PDC plan's DRS ops (the PCC phase's are its prefix; their rows are still in Y)
+    const double2* steer;   // [n_grid][N_RX] steering vectors a_r(az_g), host-computed in double
+    uint32_t n_grid, cyclic;
+    double az0, step;       // az_g = az0 + g step
+    rx_aoa_row* rows;       // [output row]
+};
+hipError_t launch_rx_aoa(const rx_aoa_args& a, uint32_t n, hipStream_t st);
+
+// What the device scan and its host twin (dnrp_aoa_estimate) share: the quadratic form, the parabola through the
+// peak and its neighbours, and the tail of a report from the scan's result.
+// R: [8][8][2] floats as stored; a: one grid point's N_RX steering entries. a^H R a in double (real: R is Hermitian)
+__host__ __device__ inline double aoa_quad(const float* R, const double2* a, uint32_t N_RX) {
+    double s = 0.0;
+#pragma unroll 1  // on the device a row at a time: all of R in double registers would cost 256 of them
+    for (uint32_t r = 0; r < N_RX; ++r) {
+        double tr = 0.0, ti = 0.0;  // (R a)_r
+        for (uint32_t c = 0; c < N_RX; ++c) {
+            const double xr = R[(r * 8 + c) * 2], xi = R[(r * 8 + c) * 2 + 1];
+            tr += xr * a[c].x - xi * a[c].y;
+            ti += xr * a[c].y + xi * a[c].x;
+        }
+        s += a[r].x * tr + a[r].y * ti;
+    }
+    return s;
+}
+__host__ __device__ inline double aoa_trace(const float* R, uint32_t N_RX) {
+    double t = 0.0;
+    for (uint32_t r = 0; r < N_RX; ++r) t += R[(r * 8 + r) * 2];
+    return t;
+}
+// the report's fields behind R and n_cells, from the normalised spectrum P [n_grid] and its first maximum i.
+// Three-point parabola through (i - 1, i, i + 1), the neighbours wrapping on a cyclic grid; none at an end point
+// of a non-cyclic grid or where the three points do not bend downwards. The offset is kept within half a step.
+__host__ __device__ inline void aoa_finish(const float* R, uint32_t N_RX, const double* P, uint32_t n_grid, uint32_t cyclic,
+                                           double az0, double step, double tr, uint32_t i, rx_aoa_row* o) {
+    double lr = 0.0, li = 0.0;
+    for (uint32_t r = 0; r + 1 < N_RX; ++r) {
+        lr += R[((r + 1) * 8 + r) * 2];
+        li += R[((r + 1) * 8 + r) * 2 + 1];
+    }
+    o->lag_re = static_cast<float>(lr);
+    o->lag_im = static_cast<float>(li);
+    o->reserved[0] = o->reserved[1] = 0;
+    if (!(tr > 0.0)) {
+        o->grid_idx = RX_AOA_NONE;
+        o->az_rad = 0.f;
+        o->peak = 0.f;
+        return;
+    }
+    double az = az0 + i * step, pk = P[i];
+    if (cyclic || (i > 0 && i + 1 < n_grid)) {
+        const double ym = P[i == 0 ? n_grid - 1 : i - 1], yp = P[i + 1 == n_grid ? 0 : i + 1], den = ym - 2.0 * pk + yp;
+        if (den < 0.0) {
+            double dl = 0.5 * (ym - yp) / den;
+            dl = dl < -0.5 ? -0.5 : dl > 0.5 ? 0.5 : dl;
+            az += dl * step;
+            pk -= 0.25 * (ym - yp) * dl;
+            if (cyclic && az < az0) az += 6.283185307179586476925;
+        }
+    }
+    o->grid_idx = i;
+    o->az_rad = static_cast<float>(az);
+    o->peak = static_cast<float>(pk);
+}
+
 
 // ---- ring-buffer window gather (ring.hip): buffer_rx_t ring -> linear windows (rx_pacer.cpp:106-143)
 constexpr int RING_PAIRS = 4;  // sample pairs per thread

@@ -11,6 +11,9 @@
 //  rx_cfo_track_kernel  one WG per packet, only with residual CFO tracking on: the mixer increment after
 //                   every DRS symbol of the phase, from the rotation between DRS symbols one period apart,
 //                   and the per-symbol table the front ends mix with (rx_synced_param.hpp:162-181).
+//  rx_aoa_kernel    one WG per packet, only with the angle-of-arrival report on, at the end of the PDC phase:
+//                   the spatial covariance of the zero-forced pilots of every DRS op of the packet and its
+//                   Bartlett scan (estimator_aoa_t, empty in the reference).
 // Y layout: [packet][N_RX][n_sym_total][Nf_pad] float2 (rx_fft_kernel).
 #include "device_common.hpp"
 #include "kernels.hpp"
@@ -382,6 +385,137 @@ __global__ void __launch_bounds__(TRACK_THREADS) rx_cfo_track_kernel(rx_cfo_args
 hipError_t launch_rx_cfo_track(const rx_cfo_args& a, uint32_t n, hipStream_t st) {
     if (!track_args_ok(a) || a.Nd > a.sym_len || !a.keep) return hipErrorInvalidValue;
     hipLaunchKernelGGL(rx_cfo_track_kernel, dim3(n), dim3(TRACK_THREADS), 0, st, a);
+    return hipGetLastError();
+}
+
+// ===================================================================== angle of arrival
+// The project's own estimator (the reference's estimator_aoa_t has empty bodies). R[a][b] sums
+// h_a conj(h_b) over every DRS cell of every stream of every op of the PDC plan, h_a the zero-forced pilot of
+// antenna a: what is common to the antennas (CFO mixing, STO derotation, the trackers' tables, amp_scale)
+// cancels. One wavefront per op, lanes over 64 consecutive cells, every antenna's cell loaded before the first
+// product; the upper triangle's products and a lane's sum over its cells of the op in float, the sums across
+// lanes and across ops (in index order, by one thread per pair) in double, R rounded to float once and mirrored.
+// Then the Bartlett scan of R as stored, in double: lanes over grid points, the argmax by wavefront 0 (the
+// lowest index among equal maxima), the parabola and the row by one lane (aoa_finish, shared with the host twin).
+constexpr uint32_t AOA_THREADS = 256;
+
+template <int NRX>
+__global__ void __launch_bounds__(AOA_THREADS) rx_aoa_kernel(rx_aoa_args A) {
+    constexpr int NP = NRX * (NRX + 1) / 2;
+    __shared__ double2 part[MAX_DOPS][NP];  // per op and pair (a <= b)
+    __shared__ double P[RX_AOA_MAX_GRID];
+    __shared__ float Rs[8 * 8 * 2];
+    const rx_drs_view& V = A.V;
+    const uint32_t pkt = rx_slot_of(V.sel, blockIdx.x), nd = V.n_drs;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, nw = AOA_THREADS / 64;
+    const size_t ast = size_t(V.n_sym_total) * V.Nf_pad;
+    const float2* Yp = V.Y + size_t(pkt) * NRX * ast;
+    rx_aoa_row* row = A.rows + rx_row_of(V.sel, blockIdx.x);
+    if (threadIdx.x < 8 * 8 * 2) Rs[threadIdx.x] = 0.f;
+    for (uint32_t d = wave; d < V.n_dops; d += nw) {
+        const drs_op op = drs_op_of(__builtin_amdgcn_readfirstlane(V.dmeta[d]));
+        const uint32_t l = __builtin_amdgcn_readfirstlane(V.dl[d]);
+        const float2* rows = Yp + size_t(l) * V.Nf_pad;
+        float2 acc[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) acc[p] = make_float2(0.f, 0.f);
+        // one loop over (stream, round of 64 cells): one round's cells in registers beside the running sums
+        const uint32_t rounds = (nd + 63) / 64, n_it = (op.tl - op.tf + 1) * rounds;
+#pragma unroll 1
+        for (uint32_t it = 0; it < n_it; ++it) {
+            const drs_stream S(V, op.par, op.tf + it / rounds);
+            const uint32_t i = (it % rounds) * 64 + lane;
+            const bool in = i < nd;
+            const uint32_t k = in ? S.k[i] : 0u;
+            const float w = in ? S.v[i] : 0.f;
+            float2 h[NRX];
+#pragma unroll
+            for (int a = 0; a < NRX; ++a) h[a] = rows[a * ast + k];
+#pragma unroll
+            for (int a = 0; a < NRX; ++a) h[a] = in ? cscale(h[a], w) : make_float2(0.f, 0.f);
+            int p = 0;
+#pragma unroll
+            for (int a = 0; a < NRX; ++a)
+#pragma unroll
+                for (int b = a; b < NRX; ++b, ++p) {
+                    const float2 c = cmulc(h[a], h[b]);
+                    acc[p].x += c.x;
+                    acc[p].y += c.y;
+                }
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            // one pair's doubles at a time (the empty statement keeps the conversions in order): all 36 pairs
+            // converted ahead of their sums cost 144 registers
+            float fx = acc[p].x, fy = acc[p].y;
+            asm volatile("" : "+v"(fx), "+v"(fy));
+            const double2 s = wave_sum2(static_cast<double>(fx), static_cast<double>(fy));
+            if (lane == 0) part[d][p] = s;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < NP) {
+        double sr = 0.0, si = 0.0;
+        for (uint32_t d = 0; d < V.n_dops; ++d) {
+            sr += part[d][threadIdx.x].x;
+            si += part[d][threadIdx.x].y;
+        }
+        uint32_t a = 0, q = threadIdx.x;  // pair index -> (a, b), a <= b
+        while (q >= NRX - a) {
+            q -= NRX - a;
+            ++a;
+        }
+        const uint32_t b = a + q;
+        const float fr = static_cast<float>(sr), fi = static_cast<float>(si);
+        Rs[(a * 8 + b) * 2] = fr;
+        if (a != b) {  // the diagonal's imaginary part stays exactly 0, the lower triangle is the exact conjugate
+            Rs[(a * 8 + b) * 2 + 1] = fi;
+            Rs[(b * 8 + a) * 2] = fr;
+            Rs[(b * 8 + a) * 2 + 1] = -fi;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 8 * 8 * 2) (&row->R[0][0][0])[threadIdx.x] = Rs[threadIdx.x];
+    const double tr = aoa_trace(Rs, NRX);
+    for (uint32_t g = threadIdx.x; g < A.n_grid; g += AOA_THREADS)
+        P[g] = tr > 0.0 ? aoa_quad(Rs, A.steer + size_t(g) * NRX, NRX) / (static_cast<double>(NRX) * tr) : 0.0;
+    __syncthreads();
+    if (wave != 0) return;
+    double best = -HUGE_VAL;
+    uint32_t bi = RX_AOA_NONE;
+    for (uint32_t g = lane; g < A.n_grid; g += 64)
+        if (P[g] > best) {
+            best = P[g];
+            bi = g;
+        }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o);
+        const uint32_t oi = __shfl_xor(bi, o);
+        if (ob > best || (ob == best && oi < bi)) {
+            best = ob;
+            bi = oi;
+        }
+    }
+    if (lane != 0) return;
+    uint32_t nc = 0;
+    for (uint32_t d = 0; d < V.n_dops; ++d) {
+        const drs_op op = drs_op_of(V.dmeta[d]);
+        nc += (op.tl - op.tf + 1) * nd;
+    }
+    row->n_cells = nc;
+    aoa_finish(Rs, NRX, P, A.n_grid, A.cyclic, A.az0, A.step, tr, bi, row);
+}
+
+hipError_t launch_rx_aoa(const rx_aoa_args& a, uint32_t n, hipStream_t st) {
+    const rx_drs_view& v = a.V;
+    if (v.n_dops > MAX_DOPS || a.n_grid == 0 || a.n_grid > RX_AOA_MAX_GRID || !a.steer || !a.rows) return hipErrorInvalidValue;
+    switch (v.N_RX) {
+        case 2: hipLaunchKernelGGL(rx_aoa_kernel<2>, dim3(n), dim3(AOA_THREADS), 0, st, a); break;
+        case 4: hipLaunchKernelGGL(rx_aoa_kernel<4>, dim3(n), dim3(AOA_THREADS), 0, st, a); break;
+        case 8: hipLaunchKernelGGL(rx_aoa_kernel<8>, dim3(n), dim3(AOA_THREADS), 0, st, a); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -180,6 +180,36 @@ MIMO_DETAIL_DTYPE = np.dtype([("N_RX", np.uint32), ("N_TS", np.uint32), ("H", np
 assert MIMO_DETAIL_DTYPE.itemsize == C.sizeof(MimoDetail)
 
 
+class AoaCfg(C.Structure):
+    """dnrp_aoa_cfg: antenna positions in carrier wavelengths and the azimuth grid of the Bartlett scan."""
+    _fields_ = [("pos", C.c_float * 2 * 8), ("az_min", C.c_float), ("az_max", C.c_float), ("n_grid", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class AoaReport(C.Structure):
+    """dnrp_aoa_report: spatial covariance of the zero-forced DRS pilots and its Bartlett scan (dnrp_rx_aoa)."""
+    _fields_ = [("R", C.c_float * 2 * 8 * 8), ("n_cells", C.c_uint32), ("grid_idx", C.c_uint32), ("az_rad", C.c_float),
+                ("peak", C.c_float), ("lag_re", C.c_float), ("lag_im", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+AOA_NONE = 0xFFFFFFFF
+AOA_REPORT_DTYPE = np.dtype([("R", np.complex64, (8, 8)), ("n_cells", np.uint32), ("grid_idx", np.uint32),
+                             ("az_rad", np.float32), ("peak", np.float32), ("lag", np.complex64),
+                             ("reserved", np.uint32, (2,))])
+assert AOA_REPORT_DTYPE.itemsize == C.sizeof(AoaReport)
+
+
+def _aoa_cfg(pos, az_min, az_max, n_grid):
+    pos = np.asarray(pos, np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 2 or not 1 <= pos.shape[0] <= 8:
+        raise ValueError("pos: [N_RX <= 8][2] antenna positions (x, y) in wavelengths")
+    cfg = AoaCfg()
+    for r in range(pos.shape[0]):
+        cfg.pos[r][0], cfg.pos[r][1] = float(pos[r, 0]), float(pos[r, 1])
+    cfg.az_min, cfg.az_max, cfg.n_grid, cfg.reserved = float(az_min), float(az_max), int(n_grid), 0
+    return cfg
+
+
 class PdcReq(C.Structure):
     """dnrp_pdc_req: PLCF-announced psdef, slot in the preceding PCC batch, network ID, PLCF type."""
     _fields_ = [("psdef", PsDef), ("pcc_index", C.c_uint32), ("network_id", C.c_uint32), ("plcf_type", C.c_uint32)]
@@ -240,7 +270,8 @@ EXPORTS = ["dnrp_ctx_create", "dnrp_ctx_destroy", "dnrp_add_network_id", "dnrp_g
            "dnrp_ctx_set_sync_icfo_search", "dnrp_ctx_get_sync_icfo_search", "dnrp_rx_sync_icfo_scores",
            "dnrp_tx_last_form", "dnrp_tx_form_for", "dnrp_ctx_set_rx_sto_tracking", "dnrp_ctx_get_rx_sto_tracking",
            "dnrp_rx_sto_track", "dnrp_ctx_set_rx_mimo_report", "dnrp_ctx_get_rx_mimo_report", "dnrp_rx_mimo_detail",
-           "dnrp_ctx_set_rx_cfo_tracking", "dnrp_ctx_get_rx_cfo_tracking", "dnrp_rx_cfo_track"]
+           "dnrp_ctx_set_rx_cfo_tracking", "dnrp_ctx_get_rx_cfo_tracking", "dnrp_rx_cfo_track",
+           "dnrp_ctx_set_rx_aoa", "dnrp_ctx_get_rx_aoa", "dnrp_rx_aoa", "dnrp_aoa_estimate"]
 
 _lib = None
 
@@ -289,6 +320,10 @@ def lib():
         L.dnrp_ctx_set_rx_mimo_report.argtypes = [P, C.c_uint32, C.c_uint32, C.c_uint32]
         L.dnrp_ctx_get_rx_mimo_report.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.dnrp_rx_mimo_detail.argtypes = [P, C.c_uint32, P, P]
+        L.dnrp_ctx_set_rx_aoa.argtypes = [P, C.POINTER(AoaCfg)]
+        L.dnrp_ctx_get_rx_aoa.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(AoaCfg)]
+        L.dnrp_rx_aoa.argtypes = [P, C.c_uint32, P, P]
+        L.dnrp_aoa_estimate.argtypes = [C.POINTER(AoaCfg), C.c_uint32, P, C.POINTER(AoaReport), P]
         L.dnrp_ring_gather.argtypes = [P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, P, C.c_uint32, P, P]
         L.dnrp_channel_batch.argtypes = [P, C.POINTER(ChannelCfg), C.c_uint32, C.c_uint32, P, C.c_uint32, C.c_uint32, P, P,
                                          P, C.c_uint32, P]
@@ -362,6 +397,22 @@ def tx_form_for(cfg, ps, codebooks, S=None, out_misalign=0, win_fraction=0.0):
     _chk(lib().dnrp_tx_form_for(C.byref(c), C.byref(ps), len(cb), C.c_void_p(cb.ctypes.data), int(S), int(out_misalign),
                                 float(win_fraction), C.byref(out)), "dnrp_tx_form_for")
     return out.as_dict()
+
+
+def aoa_estimate(pos, az_min, az_max, n_grid, R, N_RX=None):
+    """Host-only: the Bartlett scan of dnrp_aoa_estimate on a covariance R (complex [N_RX, N_RX], or the report's
+    [8, 8]; rounded to complex64, as the device stores it) with the code the device scan runs. Returns a dict:
+    grid_idx, az_rad, peak, lag (complex) and spectrum float32 [n_grid]."""
+    R = np.asarray(R)
+    n = int(N_RX) if N_RX is not None else len(np.asarray(pos))
+    R8 = np.zeros((8, 8), np.complex64)
+    R8[:n, :n] = R[:n, :n]
+    cfg, out = _aoa_cfg(pos, az_min, az_max, n_grid), AoaReport()
+    spec = np.zeros(max(int(n_grid), 1), np.float32)
+    _chk(lib().dnrp_aoa_estimate(C.byref(cfg), n, C.c_void_p(R8.ctypes.data), C.byref(out), C.c_void_p(spec.ctypes.data)),
+         "dnrp_aoa_estimate")
+    return dict(grid_idx=out.grid_idx, az_rad=out.az_rad, peak=out.peak, lag=complex(out.lag_re, out.lag_im),
+                spectrum=spec[:int(n_grid)])
 
 
 def query_table(name, *args):
@@ -636,6 +687,35 @@ class Phy:
         out = np.zeros(int(m), MIMO_DETAIL_DTYPE)
         _chk(lib().dnrp_rx_mimo_detail(self._ctx, int(m), C.c_void_p(out.ctypes.data) if m else None, _stream_ptr(stream)),
              "dnrp_rx_mimo_detail")
+        self.sync(stream)
+        return out
+
+    def set_rx_aoa(self, pos, az_min=-np.pi / 2, az_max=np.pi / 2, n_grid=181):
+        """dnrp_ctx_set_rx_aoa: every later rx_pdc_batch reports, per request, the spatial covariance of the
+        zero-forced DRS pilots and its Bartlett scan over n_grid azimuths in [az_min, az_max] (cyclic where the
+        span is 2 pi) for antennas at pos [N_RX][2] (x, y) in carrier wavelengths (rx_aoa). set_rx_aoa(None), the
+        default, turns it off."""
+        if pos is None:
+            _chk(lib().dnrp_ctx_set_rx_aoa(self._ctx, None), "dnrp_ctx_set_rx_aoa")
+            return
+        cfg = _aoa_cfg(pos, az_min, az_max, n_grid)
+        _chk(lib().dnrp_ctx_set_rx_aoa(self._ctx, C.byref(cfg)), "dnrp_ctx_set_rx_aoa")
+
+    def rx_aoa_cfg(self):
+        """dnrp_ctx_get_rx_aoa: None while off, else (pos float32 [8, 2], az_min, az_max, n_grid)."""
+        on, cfg = C.c_uint32(), AoaCfg()
+        _chk(lib().dnrp_ctx_get_rx_aoa(self._ctx, C.byref(on), C.byref(cfg)), "dnrp_ctx_get_rx_aoa")
+        if not on.value:
+            return None
+        return np.ctypeslib.as_array(cfg.pos).astype(np.float32).reshape(8, 2), cfg.az_min, cfg.az_max, cfg.n_grid
+
+    def rx_aoa(self, m, stream=None):
+        """dnrp_rx_aoa: numpy record array [m] of AOA_REPORT_DTYPE (R complex64 [m, 8, 8], lag complex64, ...),
+        row r = request r of the latest rx_pdc_batch, which ran with set_rx_aoa on. Synchronises the stream
+        before it returns."""
+        out = np.zeros(int(m), AOA_REPORT_DTYPE)
+        _chk(lib().dnrp_rx_aoa(self._ctx, int(m), C.c_void_p(out.ctypes.data) if m else None, _stream_ptr(stream)),
+             "dnrp_rx_aoa")
         self.sync(stream)
         return out
 

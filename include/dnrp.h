@@ -54,7 +54,8 @@ extern "C" {
 #define DNRP_ESTATE (-7)      /* dnrp_rx_pdc_batch without a preceding dnrp_rx_pcc_batch; dnrp_rx_sync_fine_peaks
                                  or dnrp_rx_sync_icfo_scores without a preceding dnrp_rx_sync_batch that ran with
                                  the setting on;
-                                 dnrp_rx_mimo_detail without a preceding dnrp_rx_pdc_batch that ran with detail = 1 */
+                                 dnrp_rx_mimo_detail without a preceding dnrp_rx_pdc_batch that ran with detail = 1;
+                                 dnrp_rx_aoa without a preceding dnrp_rx_pdc_batch that ran with the report on */
 
 typedef struct dnrp_ctx dnrp_ctx;
 
@@ -564,6 +565,63 @@ typedef struct {
 } dnrp_mimo_detail;
 
 int dnrp_rx_mimo_detail(dnrp_ctx* ctx, uint32_t m, dnrp_mimo_detail* out, void* stream);
+
+/*
+ * Angle-of-arrival report from the DRS pilots <- estimator_aoa_t (lib/include/dectnrp/phy/rx/rx_synced/aoa/
+ * estimator_aoa.hpp; rx_synced.cpp:133, 251), whose reset / process_stf / process_drs bodies are empty in the
+ * reference. The estimator is this project's own:
+ *   R[a][b] = sum h_a conj(h_b) over every DRS cell of every transmit stream of every DRS symbol of the packet
+ *             (the PCC phase's included), h_a the zero-forced pilot w y of RX antenna a. Whatever is common to
+ *             the antennas (CFO mixing, STO derotation, residual tracking, the amplitude scale) cancels.
+ *             Products in float, sums across lanes and DRS symbols in double in a fixed order (bit-identical
+ *             from run to run), stored as float; R[b][a] = conj(R[a][b]) exactly, the diagonal's imaginary
+ *             parts exactly 0, rows and columns at index >= N_RX zero. n_cells: cells summed per antenna.
+ *   array     antenna r at pos[r] = (x_r, y_r) in carrier wavelengths; steering vector a_r(az) =
+ *             exp(j 2 pi (x_r cos az + y_r sin az)). Narrowband: one wavelength for the whole occupied band
+ *             (at most 1.5 % of the carrier). Entries of pos at index >= N_RX are not used but must be finite.
+ *   scan      Bartlett: P(g) = a(az_g)^H R a(az_g) / (N_RX tr R) on n_grid azimuths, az_g = az_min + g step,
+ *             step = (az_max - az_min) / (n_grid - 1), end points included; where az_max - az_min is 2 pi (within
+ *             1e-5, the rounding of the float end points) the grid is cyclic, step = 2 pi / n_grid, without the
+ *             end point. The steering table is computed in double on the host when the setting is made; the
+ *             quadratic form runs in double on the device from R as stored. grid_idx: the first maximum
+ *             (strictly greater, from 0). az_rad / peak: the vertex of the parabola through the maximum and its
+ *             two neighbours (wrapping on a cyclic grid, az_rad brought back to >= az_min there); the grid point
+ *             itself at an end point of a non-cyclic grid. tr R = 0: az_rad = 0, peak = 0, grid_idx = 0xFFFFFFFF.
+ *   lag       lag_re + j lag_im = sum_a R[a + 1][a]: for a uniform line of spacing d along y its argument is
+ *             2 pi d sin az, the caller takes asin(arg / (2 pi d)).
+ * dnrp_ctx_set_rx_aoa: cfg NULL = off (the default: no launch, allocation or copy, LLRs and reports byte for
+ * byte as before). On, every later dnrp_rx_pdc_batch runs rx_aoa_kernel (timer "rx_aoa") for every request, with
+ * or without `rep`; the fused PDC receiver is not chosen (its DRS bins are not in Y), every other path and the
+ * MMSE receiver stay selectable. Read once per dnrp_rx_pdc_batch: a call in flight keeps the setting it read.
+ * DNRP_EINVAL for a NULL context, a context with N_TX_max < 2, non-finite values, n_grid outside 8..512,
+ * az_max <= az_min, az_max - az_min > 2 pi (+ 1e-5) or reserved != 0; a refused call changes nothing.
+ * dnrp_ctx_get_rx_aoa: *on and, where on, *cfg (either may be NULL).
+ * dnrp_rx_aoa: stream-ordered copy of rows 0..m-1 of the latest dnrp_rx_pdc_batch, in request order, valid once
+ * `stream` has been synchronised. DNRP_ESTATE if that call did not run the kernel or there was none;
+ * DNRP_EINVAL for NULL pointers, m = 0 or m above that call's m.
+ * dnrp_aoa_estimate: host only, no context or device: everything of *out but R and n_cells (left as they are)
+ * from R [8][8][2] floats (re, im; the layout of dnrp_aoa_report::R) for N_RX in 2..8 antennas, by the code
+ * that builds the table the setter uploads and the scan code the kernel runs; spectrum: NULL or [n_grid], P(g)
+ * (all 0 where tr R = 0). DNRP_EINVAL for NULL cfg / R / out, N_RX outside 2..8 or a cfg the setter refuses.
+ */
+typedef struct {
+    float pos[8][2];          /* (x, y) of every RX antenna in carrier wavelengths */
+    float az_min, az_max;     /* rad */
+    uint32_t n_grid;          /* 8..512 */
+    uint32_t reserved;        /* 0 */
+} dnrp_aoa_cfg;
+
+typedef struct {
+    float R[8][8][2];         /* [a][b] (re, im) */
+    uint32_t n_cells, grid_idx;
+    float az_rad, peak, lag_re, lag_im;
+    uint32_t reserved[2];
+} dnrp_aoa_report;
+
+int dnrp_ctx_set_rx_aoa(dnrp_ctx* ctx, const dnrp_aoa_cfg* cfg);
+int dnrp_ctx_get_rx_aoa(const dnrp_ctx* ctx, uint32_t* on, dnrp_aoa_cfg* cfg);
+int dnrp_rx_aoa(dnrp_ctx* ctx, uint32_t m, dnrp_aoa_report* out, void* stream);
+int dnrp_aoa_estimate(const dnrp_aoa_cfg* cfg, uint32_t N_RX, const float* R, dnrp_aoa_report* out, float* spectrum);
 
 /*
  * Ring-buffer window gather <- rx_pacer_t's wrap copy (rx_pacer.cpp:106-143) over the per-antenna
