@@ -3,6 +3,7 @@
 #pragma once
 
 #include "experiments.hpp"
+#include "wfft_index.hpp"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -495,13 +496,22 @@ __device__ void fft_store(float2* x_, float2* y_, const float2* tw, const fft_pl
 // first pass starts from registers, two exchanges go through the wave's own LDS buffer xb
 // (>= 1088 float2, index padded i + i/16: conflict-free b64 writes, <= 2-way reads), no workgroup
 // barrier. tw: forward twiddles exp(-2 pi i j / 1024) (LDS or global).
-constexpr uint32_t WFFT_XB = 1024 + 64;
+// WFFT_XB, wfft_pad, wfft_off and the four access patterns: wfft_index.hpp
 
-// exchange slot of element i: padded i + i / 16 (default: conflict-free b64 writes of pass 1 and 2,
-// 2-way ds_read_b64 conflicts in passes 2 and 3 -- slots 0 and 32 of a half-wave share a bank) or, with
-// XS_WFFT_SWZ (experiments.hpp), i ^ ((i >> 4) & 15): conflict-free for all four exchange patterns, but the XOR makes
-// the slot lane-dependent per instruction (address VALU instead of immediate offsets)
-__device__ __forceinline__ uint32_t wfft_pad(uint32_t i) { return experiment(XS_WFFT_SWZ) ? (i ^ ((i >> 4) & 15u)) : i + (i >> 4); }
+// The exchange slots of one access pattern (wfft_index.hpp): ex[c] is the slot of element i0 + c for a c
+// that is a constant once the loops are unrolled: one padded lane base, immediate offsets
+struct wfft_ex {
+    float2* p;
+    __device__ __forceinline__ wfft_ex(float2* xb, uint32_t i0) : p(xb + wfft_pad(i0)) {}
+    __device__ __forceinline__ float2& operator[](uint32_t c) const { return p[wfft_off(c)]; }
+};
+// pass 3 reads through the wfft_ex of pass 2 (yl): the same lane base
+constexpr bool wfft_r3_shares_r2_base() {
+    for (uint32_t lane = 0; lane < 64; ++lane)
+        if (wfft_r3_base(lane) != wfft_r2_base(lane)) return false;
+    return true;
+}
+static_assert(wfft_r3_shares_r2_base(), "pass 3 reads through pass 2's lane base (yl)");
 
 template <int SIGN>
 __device__ __forceinline__ float2 wfft_tw(const float2* tw, uint32_t e) {
@@ -726,20 +736,26 @@ template <int SIGN>
 __device__ __forceinline__ void wave_fft1024(float2 (&v)[16], float2* xb, const float2* tw, uint32_t lane) {
     // pass 1: radix 16, Ns = 1, butterfly j = lane on x[j + 64 r] -> y[16 j + k]
     dft16<SIGN>(v);
+    {
+        const wfft_ex y(xb, wfft_w1_base(lane));
 #pragma unroll
-    for (int k = 0; k < 16; ++k) xb[wfft_pad(16 * lane + k)] = v[k];
+        for (int k = 0; k < 16; ++k) y[wfft_w1_off(k)] = v[k];
+    }
     __builtin_amdgcn_wave_barrier();
     // pass 2: radix 16, Ns = 16: reads y[j + 64 r], twiddle W256^(r kk), writes z[(j/16) 256 + kk + 16 k]
     const uint32_t kk = lane & 15u;
+    const wfft_ex yl(xb, wfft_r2_base(lane));
 #pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] = xb[wfft_pad(lane + 64 * r)];
+    for (int r = 0; r < 16; ++r) v[r] = yl[wfft_r2_off(r)];
 #pragma unroll
     for (int r = 1; r < 16; ++r) v[r] = cmul(v[r], wfft_tw<SIGN>(tw, 4 * r * kk));
     dft16<SIGN>(v);
     __builtin_amdgcn_wave_barrier();
-    const uint32_t zb = (lane >> 4) * 256 + kk;
+    {
+        const wfft_ex z(xb, wfft_w2_base(lane));
 #pragma unroll
-    for (int k = 0; k < 16; ++k) xb[wfft_pad(zb + 16 * k)] = v[k];
+        for (int k = 0; k < 16; ++k) z[wfft_w2_off(k)] = v[k];
+    }
     __builtin_amdgcn_wave_barrier();
     // pass 3: radix 4, Ns = 256: butterflies j = lane + 64 b read z[j + 256 r], twiddle W1024^(r j),
     // write X[j + 256 r] = X[lane + 64 (b + 4 r)] -> v[b + 4 r]
@@ -747,7 +763,7 @@ __device__ __forceinline__ void wave_fft1024(float2 (&v)[16], float2* xb, const 
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
         const uint32_t j = lane + 64 * b;
-        float2 a0 = xb[wfft_pad(j)], a1 = xb[wfft_pad(j + 256)], a2 = xb[wfft_pad(j + 512)], a3 = xb[wfft_pad(j + 768)];
+        float2 a0 = yl[wfft_r3_off(b, 0)], a1 = yl[wfft_r3_off(b, 1)], a2 = yl[wfft_r3_off(b, 2)], a3 = yl[wfft_r3_off(b, 3)];
         a1 = cmul(a1, wfft_tw<SIGN>(tw, j));
         a2 = cmul(a2, wfft_tw<SIGN>(tw, 2 * j));
         a3 = cmul(a3, wfft_tw<SIGN>(tw, 3 * j));
@@ -772,12 +788,15 @@ template <int SIGN>
 __device__ __forceinline__ void wave_fft1024_rt(float2 (&v)[16], float2* xb, float2 w1, float2 wl, uint32_t lane) {
     constexpr float C1 = 0.92387953251128675613f, S1 = 0.38268343236508977173f, R2 = 0.70710678118654752440f;
     dft16<SIGN>(v);
+    {
+        const wfft_ex y(xb, wfft_w1_base(lane));
 #pragma unroll
-    for (int k = 0; k < 16; ++k) xb[wfft_pad(16 * lane + k)] = v[k];
+        for (int k = 0; k < 16; ++k) y[wfft_w1_off(k)] = v[k];
+    }
     __builtin_amdgcn_wave_barrier();
-    const uint32_t kk = lane & 15u;
+    const wfft_ex yl(xb, wfft_r2_base(lane));
 #pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] = xb[wfft_pad(lane + 64 * r)];
+    for (int r = 0; r < 16; ++r) v[r] = yl[wfft_r2_off(r)];
     {
         float2 w[16];
         w[1] = w1;
@@ -800,19 +819,20 @@ __device__ __forceinline__ void wave_fft1024_rt(float2 (&v)[16], float2* xb, flo
     }
     dft16<SIGN>(v);
     __builtin_amdgcn_wave_barrier();
-    const uint32_t zb = (lane >> 4) * 256 + kk;
+    {
+        const wfft_ex z(xb, wfft_w2_base(lane));
 #pragma unroll
-    for (int k = 0; k < 16; ++k) xb[wfft_pad(zb + 16 * k)] = v[k];
+        for (int k = 0; k < 16; ++k) z[wfft_w2_off(k)] = v[k];
+    }
     __builtin_amdgcn_wave_barrier();
     float2 o[16];
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-        const uint32_t j = lane + 64 * b;
         const float cb = b == 0 ? 1.f : b == 1 ? C1 : b == 2 ? R2 : S1;
         const float sb = b == 0 ? 0.f : b == 1 ? S1 : b == 2 ? R2 : C1;
         const float2 e1 = b == 0 ? wl : cmul(wl, make_float2(cb, SIGN * sb));
         const float2 e2 = cmul(e1, e1), e3 = cmul(e2, e1);
-        float2 a0 = xb[wfft_pad(j)], a1 = xb[wfft_pad(j + 256)], a2 = xb[wfft_pad(j + 512)], a3 = xb[wfft_pad(j + 768)];
+        float2 a0 = yl[wfft_r3_off(b, 0)], a1 = yl[wfft_r3_off(b, 1)], a2 = yl[wfft_r3_off(b, 2)], a3 = yl[wfft_r3_off(b, 3)];
         a1 = cmul(a1, e1);
         a2 = cmul(a2, e2);
         a3 = cmul(a3, e3);

@@ -36,8 +36,8 @@ enum xs_bit : unsigned {
     // TX: a DF bin's value is its code (the bin mapping's share of the kernel)
     XS_TX_TRIVIAL_BINS = 1u << 12,
     // ---- measured alternatives (same results, slower)
-    // wave FFT exchange slots XOR-swizzled instead of padded (conflict-free, +1-2 % TX)
-    XS_WFFT_SWZ = 1u << 14,
+    // (bit 14, XS_WFFT_SWZ, retired: the wave FFT's exchange slots XOR-swizzled instead of padded measured
+    // +1-2 % TX, and its lane-dependent slots cannot share one lane base: DESIGN 6.2)
     // 256-QAM TX constellation from a separable 16-level table (two conflict-free reads, +3 % TX); the
     // pair-testing and single-stream forms only (the one-hot forms index the full table, kernels.hpp OH_*)
     XS_TX_QLEV = 1u << 15,

@@ -616,7 +616,7 @@ __global__ void __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu
         rx_resample_ct<LR, MR, HLR>(A, rx_cfo_of(A, in, S, A.STF_CP + Nd, pkt, l), sp, R, lane);
         // one instantiation of the (large, unrolled) FFT for both kinds of symbol: instruction cache
         const bool to_y = !A.no_y;
-        rx_fft_bins<RT>(A, rx_sto_of(A, S, pkt, l), R, lane, [&](uint32_t k, float2 v) {
+        rx_fft_bins<RT, RX_MIX_PAD>(A, rx_sto_of(A, S, pkt, l), R, lane, [&](uint32_t k, float2 v) {
             if (to_y) Yrow[k] = v;
             if (drs) R[k] = v;
         }, w1, wl);
@@ -733,7 +733,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) rx
             row_rsrc(A.Y + ((size_t(pkt) * A.N_RX + a) * A.n_sym_total + l) * A.Nf_pad, to_y ? A.Nf_pad * 8u : 0u);
         const bool drs = so != 0xFFFFu;
         if constexpr (!experiment(XS_FE_SKIP_FIR)) rx_resample_ct<LR, MR, HLR>(A, rx_cfo_of(A, in, S, A.STF_CP + 1024, pkt, l), sp, R, lane);
-        rx_fft_bins<true>(A, rx_sto_of(A, S, pkt, l), R, lane, [&](uint32_t k, float2 v) {
+        rx_fft_bins<true, RX_MIX_PAD>(A, rx_sto_of(A, S, pkt, l), R, lane, [&](uint32_t k, float2 v) {
             // Y is written once and read by the next launch: nontemporal stores when that launch
             // comes after the whole batch, plain ones when it follows within a cache-sized group
             typedef uint32_t u2v __attribute__((ext_vector_type(2)));

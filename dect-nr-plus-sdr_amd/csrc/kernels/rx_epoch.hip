@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(EP_THREADS) __attribute__((amdgpu_waves_per_eu
             // plain pointer stores: with the stores through a row descriptor (as in rx_fft_wave_ct_kernel) this
             // kernel's build moved 2 of 4.4 million LLRs of a C4 chunk by one LSB (profiles/r09)
             float2* Yrow = F.Y + ((yimg * NRX + a) * F.n_sym_total + l) * F.Nf_pad;
-            rx_fft_bins<true>(F, rx_sto_of(F, S, pkt, l), R, lane, [&](uint32_t k, float2 v) {
+            rx_fft_bins<true, RX_MIX_PAD>(F, rx_sto_of(F, S, pkt, l), R, lane, [&](uint32_t k, float2 v) {
                 if constexpr (DNRP_EP_YNT) {
                     typedef float f2v __attribute__((ext_vector_type(2)));
                     __builtin_nontemporal_store(f2v{v.x, v.y}, reinterpret_cast<f2v*>(Yrow + k));

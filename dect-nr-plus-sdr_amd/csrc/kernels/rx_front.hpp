@@ -33,10 +33,10 @@ template <int LR, int MR, int HLR>
 __device__ __forceinline__ rx_span_t rx_span(const rx_front_args& A, uint32_t l) {
     constexpr int W = pp_direct<LR, MR, HLR>::W;
     rx_span_t s;
-    const uint32_t n_stf = A.STF_CP + 1024;
-    s.m0 = static_cast<int>(n_stf + (l - 1) * (A.CP + 1024) + A.CP);  // first output of symbol l
-    s.qb0 = (s.m0 - static_cast<int>(A.m_star)) / LR;                  // m0 >= m_star
-    s.qb1 = (s.m0 + 1024 - static_cast<int>(A.m_star) + LR - 1) / LR;
+    const rx_blocks_t b = rx_blocks(A.STF_CP, A.CP, A.m_star, l, LR);  // first output of symbol l, its blocks
+    s.m0 = b.m0;
+    s.qb0 = b.qb0;
+    s.qb1 = b.qb1;
     s.in0 = static_cast<int64_t>(A.p_star) + int64_t(MR) * s.qb0 - HLR;
     s.n_in = static_cast<uint32_t>(MR * (s.qb1 - 1 - s.qb0) + W);
     return s;
@@ -54,17 +54,20 @@ __device__ __forceinline__ double2 rx_cfo_of(const rx_front_args& A, const rx_pk
     return A.cfo_sym ? A.cfo_sym[size_t(slot) * A.n_sym_total + l] : make_double2(static_cast<double>(n_stf) * in.inc0, S.inc1);
 }
 
-// R[i] = input in0 + i (staged), i < n_in  ->  R[j] = mixed output m0 + j, j < 1024; mix: rx_cfo_of
+// R[i] = input in0 + i (staged), i < n_in  ->  R[RX_MIX_PAD + j] = mixed output m0 + j, j < 1024 (every
+// block stores all its LR outputs, those outside the symbol into the pad slots: wfft_index.hpp); mix: rx_cfo_of
 template <int LR, int MR, int HLR>
 __device__ __forceinline__ void rx_resample_ct(const rx_front_args& A, const double2 mix,
                                                const rx_span_t& sp, float2* R, uint32_t lane) {
     using PD = pp_direct<LR, MR, HLR>;
     static_assert(taps_rx_9_10::L == LR && taps_rx_9_10::M == MR && taps_rx_9_10::HL == HLR, "generated taps");
-    constexpr int BR = (1024 + 2 * LR) / LR / 64 + 1;  // block rounds per lane
+    constexpr int BR = rx_block_rounds(LR);  // block rounds per lane
     // the outputs of round rd land below every input a later round reads (block q writes
     // R[< LR (q + 1)] and later blocks read from R[MR q'] with q' >= q + 64), so each round stores
     // its outputs before the next round loads its windows
-    static_assert(LR * (64 + 1) <= MR * 64, "round outputs stay below the next round's windows");
+    static_assert(LR * (64 + 1) + RX_MIX_PAD <= MR * 64, "round outputs stay below the next round's windows");
+    static_assert(LR - 1 <= RX_MIX_PAD && 1024 + 2 * RX_MIX_PAD <= WFFT_XB, "pad slots inside the region");
+    static_assert(BR == rx_block_rounds(LR) && (1024 + 2 * LR - 2) / LR + 1 <= 64 * BR, "BR rounds hold a symbol's blocks");
     const int n_stf = static_cast<int>(A.STF_CP + 1024);
     const double phi_stf = mix.x;  // mixer phase at the first data sample
     const float2 step1 = phasor(mix.y);
@@ -84,10 +87,10 @@ __device__ __forceinline__ void rx_resample_ct(const rx_front_args& A, const dou
         if (q < sp.qb1) {
             const int mb = static_cast<int>(A.m_star) + LR * q;
             float2 r = phasor(phi_stf + static_cast<double>(mb - n_stf) * mix.y);
+            float2* out = R + rx_mix_slot(static_cast<int>(A.m_star), LR, q, 0, sp.m0);  // >= R (mb > m0 - LR)
 #pragma unroll
             for (int k = 0; k < LR; ++k) {
-                const uint32_t idx = static_cast<uint32_t>(mb + k - sp.m0);
-                if (idx < 1024) R[idx] = cmul(y[k], r);
+                out[k] = cmul(y[k], r);
                 r = cmul(r, step1);
             }
         }
@@ -95,7 +98,8 @@ __device__ __forceinline__ void rx_resample_ct(const rx_front_args& A, const dou
     }
 }
 
-// wave FFT of R[0..1024) (R also serves as the exchange buffer, >= WFFT_XB float2) and the occupied
+// wave FFT of R[OFF .. OFF + 1024) (OFF: RX_MIX_PAD behind rx_resample_ct, 0 behind the table-tap
+// resampler; R also serves as the exchange buffer, >= WFFT_XB float2) and the occupied
 // bins: FFT bin n -> subcarrier index k (n <= N/2: k = n + N/2; upper half: k = n - off_lower),
 // amplitude sqrt(N_b_OCC)/N_b_DFT_os, STO derotation exp(j sto_inc (k - N/2)) by two running
 // phasors stepped by 64 bins (the amplitude folded into them). put(k, value) for every k in [0, N_b_OCC]; R is free again when
@@ -103,12 +107,12 @@ __device__ __forceinline__ void rx_resample_ct(const rx_front_args& A, const dou
 // RT: wave_fft1024_rt with the lane's two twiddles w1 = W^(4 (lane & 15)), wl = W^lane loaded by the
 // caller (e.g. before its input staging) instead of 27 twiddle loads inside the passes
 // sto_inc: the symbol's STO increment per subcarrier (rx_sto_of: the packet's, or the tracking table's)
-template <bool RT = false, class Put>
+template <bool RT = false, uint32_t OFF = 0, class Put>
 __device__ __forceinline__ void rx_fft_bins(const rx_front_args& A, const double sto_inc, float2* R, uint32_t lane,
                                             Put&& put, float2 w1 = float2{}, float2 wl = float2{}) {
     float2 v[16];
 #pragma unroll
-    for (int m = 0; m < 16; ++m) v[m] = R[lane + 64 * m];
+    for (int m = 0; m < 16; ++m) v[m] = R[OFF + lane + 64 * m];
     __builtin_amdgcn_wave_barrier();
     if constexpr (experiment(XS_FE_SKIP_FFT))
         ;

@@ -149,7 +149,7 @@ __global__ void __launch_bounds__(64 * NRX) __attribute__((amdgpu_waves_per_eu(N
         stage_span_lo<20>(R, src, sp.in0, sp.n_in, q_lo, q_hi, lane, 64);
         __builtin_amdgcn_wave_barrier();
         rx_resample_ct<FL, FM, FHL>(F, make_double2(static_cast<double>(F.STF_CP + 1024) * in.inc0, S.inc1), sp, R, lane);
-        rx_fft_bins<true>(F, S.sto_inc, R, lane, [&](uint32_t k, float2 v) { R[k] = v; }, w1, wl);
+        rx_fft_bins<true, RX_MIX_PAD>(F, S.sto_inc, R, lane, [&](uint32_t k, float2 v) { R[k] = v; }, w1, wl);
     }
     __syncthreads();
 
